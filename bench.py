@@ -278,6 +278,27 @@ def live_traffic(args, epochs):
                    "5-step child run of this workload; FETCH_SIZE KiB x 1024 x 2 (gfx950 counts 128-B requests as 64 B) + WRITE_SIZE KiB x 1024")
 
 
+DUMP_LIMIT = 60 << 20   # --dump-outputs: bytes of array data (under 64 MB with the .npy headers)
+
+
+def dump_outputs(out_dir, arrays, epochs):
+    """--dump-outputs: write each array as <out_dir>/<name>.npy, float64 where the output is float64 and float32 otherwise (integer outputs
+    are small and exact in float32).  Every array holds `epochs` rows per block (the gathered occupancy: one block per rank).  When they
+    come to more than DUMP_LIMIT bytes, every array keeps the same fixed, seeded sample of epochs (in every block), and the sampled epoch
+    numbers are written as epochs.npy."""
+    import numpy as np
+    arrays = {k: np.ascontiguousarray(a, dtype=np.float64 if a.dtype == np.float64 else np.float32) for k, a in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT:
+        per_epoch = total // epochs + 8                   # (+ its entry in epochs.npy)
+        keep = np.sort(np.random.default_rng(0xC0FFEE).choice(epochs, DUMP_LIMIT // per_epoch, replace=False))
+        arrays = {k: a[(np.arange(a.shape[0] // epochs)[:, None] * epochs + keep).ravel()] for k, a in arrays.items()}
+        arrays["epochs"] = keep.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -321,9 +342,15 @@ def main():
     ap.add_argument("--stage-timeout", type=float, default=300.0,
                     help="N > 1: seconds a rank may spend in one stage of the run (gloo collectives and the watchdog): a hung or dead "
                          "peer ends the job with a non-zero exit within this time")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last timed launch returned to its caller as DIR/<name>.npy (rank 0): "
+                         "features, decision, occupancy, ann_out (ANN decision only) and, at N > 1, occupancy_gathered; float32 / "
+                         "float64, at most 64 MB in all (a fixed, seeded sample of epochs beyond that, numbered in epochs.npy)")
     ap.add_argument("--traffic-json", default=os.path.join(ROOT, "profiles", "hbm_traffic.json"))
     ap.add_argument("--valu-json", default=os.path.join(ROOT, "profiles", "valu_counters.json"))
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` without a launcher: start the N rank processes ourselves.  This process has made no GPU
@@ -601,6 +628,14 @@ def main():
         torch.cuda.synchronize()
         if not np.array_equal(ex.gathered_host(last)[rank * E:(rank + 1) * E], occ_host):
             raise SystemExit(f"bench: rank {rank}: gathered occupancy differs from the local block")
+    if args.dump_outputs and rank == 0:
+        torch.cuda.synchronize()
+        dumped = {"features": feats.cpu().numpy(), "decision": dec.cpu().numpy(), "occupancy": occ_host}
+        if cfg.decide == cs.DECIDE_ANN:      # (the threshold kernels leave ann_out unwritten)
+            dumped["ann_out"] = ann.cpu().numpy()
+        if ex is not None:
+            dumped["occupancy_gathered"] = ex.gathered_host(last)
+        dump_outputs(args.dump_outputs, dumped, E)
 
     def committed(path, key):
         if not os.path.exists(path):

@@ -11,17 +11,17 @@ sys.path.insert(0, ROOT)
 
 def pytest_configure(config):
     config.addinivalue_line("markers", "gpu: needs a real MI355X (run with -m gpu on the GPU box)")
-    config.addinivalue_line("markers", "gpu_first: a GPU test whose EIGHT rank processes share the box's one GPU: runs before this "
+    config.addinivalue_line("markers", "gpu_first: a GPU test whose rank processes share the box's one GPU: runs before this "
                                        "process opens the device itself (see pytest_collection_modifyitems)")
 
 
 def pytest_collection_modifyitems(config, items):
-    """The driver hands compute queues to 8 processes at a time (amdgpu hws_max_conc_proc).  The 8-rank rehearsals of BASELINE.json
-    configs[4] put eight rank processes on the one GPU and gather in lock step over the stand-in wire; with a NINTH process holding the
-    device — this pytest process, once any in-process GPU test has run — the scheduler time-slices whole processes and every lock-step
-    gather waits a scheduling round: measured 3.9 s -> 43 s for the same command, and beyond the stage watchdog with more queues open
-    (profiles/r06_nine_gpu_processes.txt).  So those tests go first, whatever files or -k expression selected them: at that point this
-    process has made no GPU call."""
+    """The multi-rank rehearsals of BASELINE.json configs[4] put several rank processes on the one GPU and gather in lock step over the
+    stand-in wire.  A further process holding the device — this pytest process, once any in-process GPU test has run — competes with
+    them for it: with eight ranks, where the driver hands compute queues to 8 processes at a time (amdgpu hws_max_conc_proc), every
+    lock-step gather waited a scheduling round, 3.9 s -> 43 s for the same command (profiles/r06_nine_gpu_processes.txt); and the
+    number of processes that may hold one GPU at once is capped.  So those tests go first, whatever files or -k expression selected
+    them: at that point this process has made no GPU call."""
     first = [it for it in items if it.get_closest_marker("gpu_first")]
     if first:
         items[:] = first + [it for it in items if not it.get_closest_marker("gpu_first")]

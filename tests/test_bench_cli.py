@@ -50,6 +50,19 @@ def test_bench_prints_one_json_line_with_roofline_and_cpu_baseline(built):
     assert d["roofline"]["kernel_ms_mean"] <= d["ms_per_step"]
 
 
+def test_bench_dump_outputs_are_the_same_on_every_run(built, tmp_path):
+    """--dump-outputs writes what the last timed launch returned, and the seeded input makes two runs of one command agree exactly."""
+    import numpy as np
+    for d in ("a", "b"):
+        assert _run("--cpu-epochs", "0", "--dump-outputs", str(tmp_path / d))["steps"] == 4
+    assert sorted(os.listdir(tmp_path / "a")) == ["decision.npy", "features.npy", "occupancy.npy"]
+    for f in os.listdir(tmp_path / "a"):
+        a, b = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert a.dtype == np.float32 and a.shape[0] == 512 and np.array_equal(a, b), f
+    occ = np.load(tmp_path / "a" / "occupancy.npy")
+    assert occ.shape == (512, 4) and occ.any() and not occ.all()
+
+
 def test_bench_default_batch_with_every_alt_leg_and_the_cpu_check(built):
     """The driver's shape: the default 8.75 GiB batch, so that the config.alt legs run (SURVEY §8(d)'s 2 GiB batch on one and on two
     streams, the unpruned kernel) — and the CPU sample check after them still reads the headline launch's results, not a leg's.
@@ -222,31 +235,32 @@ def test_bench_self_launches_two_ranks_without_a_launcher(built):
 @pytest.mark.gpu_first
 @pytest.mark.parametrize("scaling", ["weak", "strong"])
 @pytest.mark.parametrize("mode", [[], ["--mode", "scan"]])
-def test_bench_cfg4_rehearsal_eight_self_launched_ranks_on_one_gpu(built, mode, scaling):
-    """BASELINE.json configs[4] as the driver will start it (`python3 bench.py --gpus 8 ...`), rehearsed with the eight ranks sharing
+def test_bench_cfg4_rehearsal_four_self_launched_ranks_on_one_gpu(built, mode, scaling):
+    """BASELINE.json configs[4] as the driver will start it (`python3 bench.py --gpus N ...`), rehearsed with four ranks sharing
     the one GPU: bench.py starts torch.distributed.run itself before it touches the GPU, gloo control plane, RCCL unique id from
-    rank 0 through the C ABI, streams sharded eight ways, crn_comm_* slots, the barriers and the max-over-ranks timing; EVERY rank
+    rank 0 through the C ABI, streams sharded four ways, crn_comm_* slots, the barriers and the max-over-ranks timing; EVERY rank
     checks that its own block sits unchanged at its place in the gathered vector (a mismatch on any rank makes the launcher, and so
     the parent, exit non-zero) and rank 0's single JSON line is relayed."""
-    # weak: 4096 epochs on every rank.  strong: 32 768 epochs in all, split eight ways — a share far below 4 GiB, so every rank
-    # alternates its launches between two streams (four exchange slots).  (Eight rank processes are all the GPU schedules at once:
-    # the test is marked gpu_first so that this pytest process is not a ninth — tests/conftest.py — and the batch is large enough
-    # that the ~50 ms clock-ramp top-up is ~200 lock-step gathers, not ~900, should a ninth process be there all the same.)
-    d = _self_launched(8, *mode, "--scaling", scaling, epochs="4096" if scaling == "weak" else "32768", cpu_epochs="32")
-    assert d["n_gpus"] == 8 and d["scaling"] == scaling and d["config"]["epochs_per_gpu"] == 4096
-    assert d["config"]["epochs_per_step_all_gpus"] == 32768 and d["config"]["streams_per_gpu"] == (2 if scaling == "strong" else 1)
-    assert d["config"]["parallelism"].startswith("stream-sharded x8") and "crn_comm_" in d["config"]["parallelism"]
+    # weak: 4096 epochs on every rank.  strong: 16 384 epochs in all, split four ways — a share far below 4 GiB, so every rank
+    # alternates its launches between two streams (four exchange slots).  (Four ranks, not the eight of an 8-GPU node: one GPU may
+    # be held by at most six processes at once.  The test is marked gpu_first so that this pytest process does not hold the device
+    # beside them — tests/conftest.py — and the batch is large enough that the ~50 ms clock-ramp top-up is ~200 lock-step gathers.)
+    n = 4
+    d = _self_launched(n, *mode, "--scaling", scaling, epochs="4096" if scaling == "weak" else str(4096 * n), cpu_epochs="32")
+    assert d["n_gpus"] == n and d["scaling"] == scaling and d["config"]["epochs_per_gpu"] == 4096
+    assert d["config"]["epochs_per_step_all_gpus"] == 4096 * n and d["config"]["streams_per_gpu"] == (2 if scaling == "strong" else 1)
+    assert d["config"]["parallelism"].startswith(f"stream-sharded x{n}") and "crn_comm_" in d["config"]["parallelism"]
     assert d["value"] > 0 and d["ms_per_step"] > 0 and d["steps"] == 4
-    _check_cpu_baseline_of_an_n_gt_1_line(d, 8)       # every N > 1 line carries the CPU figure (rank 0 measures it after the timed region)
-    # the line proves what the collective saw: eight ranks, every one of them counted eight, in rank order, each with its gathers,
-    # and which physical GPU each was bound to (here one GPU eight times: the stand-in, version 0, is the only library allowed that)
+    _check_cpu_baseline_of_an_n_gt_1_line(d, n)       # every N > 1 line carries the CPU figure (rank 0 measures it after the timed region)
+    # the line proves what the collective saw: four ranks, every one of them counted four, in rank order, each with its gathers,
+    # and which physical GPU each was bound to (here one GPU four times: the stand-in, version 0, is the only library allowed that)
     r = d["config"]["rccl"]
-    assert r["nranks"] == 8 and r["nranks_seen_by_every_rank"] == [8] and r["user_ranks"] == list(range(8)) and len(r["devices"]) == 8
-    assert len(r["pci_bus_ids"]) == 8 and all(isinstance(b, str) and len(b) >= 7 and b.count(":") == 2 for b in r["pci_bus_ids"])
+    assert r["nranks"] == n and r["nranks_seen_by_every_rank"] == [n] and r["user_ranks"] == list(range(n)) and len(r["devices"]) == n
+    assert len(r["pci_bus_ids"]) == n and all(isinstance(b, str) and len(b) >= 7 and b.count(":") == 2 for b in r["pci_bus_ids"])
     assert len(set(r["pci_bus_ids"])) == 1
     assert "fake_rccl_mp" in r["library"] and r["version"] == 0          # (the stand-in says so)
     pr = d["roofline"]["per_rank"]
-    assert len(pr["kernel_ms_mean"]) == 8 and pr["kernel_ms_mean_min"] <= pr["kernel_ms_mean_max"] and 0 <= pr["slowest_rank"] < 8
+    assert len(pr["kernel_ms_mean"]) == n and pr["kernel_ms_mean_min"] <= pr["kernel_ms_mean_max"] and 0 <= pr["slowest_rank"] < n
     assert 0 < pr["frac_slowest_rank"] <= pr["frac_fastest_rank"]
     assert ("two streams" in d["roofline"]["events"]) == (scaling == "strong")
     if mode:

@@ -163,15 +163,55 @@ def test_watchdog_ends_a_rank_stuck_in_a_stage():
     assert r.returncode == 0, r.stderr
 
 
-def test_eight_rank_rehearsals_are_collected_ahead_of_everything_that_opens_the_device():
-    """tests/conftest.py moves the gpu_first tests (eight rank processes on the one GPU) to the front of ANY selection, so that the pytest
-    process — which opens the device in its first in-process GPU test — is never a ninth GPU process beside them
+def test_rank_rehearsals_are_collected_ahead_of_everything_that_opens_the_device():
+    """tests/conftest.py moves the gpu_first tests (several rank processes on the one GPU) to the front of ANY selection, so that the
+    pytest process — which opens the device in its first in-process GPU test — never holds the device beside them
     (profiles/r06_nine_gpu_processes.txt).  Here: files named in the opposite order."""
     r = subprocess.run([sys.executable, "-m", "pytest", "--collect-only", "-q", "-m", "gpu", "-p", "no:cacheprovider",
                         os.path.join(ROOT, "tests", "test_zz_roofline_floors.py"), os.path.join(ROOT, "tests", "test_golden.py"),
                         os.path.join(ROOT, "tests", "test_bench_cli.py")], capture_output=True, text=True, timeout=300, cwd=ROOT)
     ids = [ln for ln in r.stdout.splitlines() if "::" in ln]
     assert r.returncode == 0 and len(ids) > 20, r.stdout[-2000:] + r.stderr[-2000:]
-    first = [i for i in ids if "cfg4_rehearsal_eight_self_launched_ranks" in i]
+    first = [i for i in ids if "cfg4_rehearsal_four_self_launched_ranks" in i]
     assert len(first) == 4 and ids[:4] == first, ids[:8]
     assert "test_zz_roofline_floors" in ids[4]           # the rest keeps the order it was given
+
+
+def test_dump_outputs_writes_every_array_whole_below_the_limit(tmp_path):
+    """--dump-outputs: one .npy per output, float64 kept, everything else as float32, values unchanged."""
+    import numpy as np
+    bench = _load_bench()
+    rng = np.random.default_rng(1)
+    out = {"features": rng.random((100, 4), dtype=np.float32), "decision": rng.integers(0, 4, 100).astype(np.int32),
+           "occupancy": rng.integers(0, 2, (100, 4)).astype(np.uint8), "ann_out": rng.random((100, 3)),
+           "occupancy_gathered": rng.integers(0, 2, (300, 4)).astype(np.uint8)}
+    bench.dump_outputs(str(tmp_path / "d"), out, 100)
+    assert sorted(os.listdir(tmp_path / "d")) == sorted(k + ".npy" for k in out)
+    for k, a in out.items():
+        got = np.load(tmp_path / "d" / f"{k}.npy")
+        assert got.dtype == (np.float64 if k == "ann_out" else np.float32) and np.array_equal(got, a)
+
+
+def test_dump_outputs_keeps_one_seeded_sample_of_epochs_above_the_limit(tmp_path, monkeypatch):
+    """Above the limit every array keeps the same epochs (in every rank's block of the gathered vector), the same ones on every run,
+    numbered in epochs.npy, and the data written stays within the limit."""
+    import numpy as np
+    bench = _load_bench()
+    monkeypatch.setattr(bench, "DUMP_LIMIT", 20000)
+    E, world = 1000, 2
+    feats = np.arange(E * 4, dtype=np.float32).reshape(E, 4)
+    gathered = np.arange(world * E * 4).reshape(world * E, 4).astype(np.uint8)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"features": feats, "occupancy_gathered": gathered}, E)
+    keep = np.load(tmp_path / "a" / "epochs.npy").astype(np.int64)
+    assert 0 < keep.size < E and np.array_equal(keep, np.unique(keep))
+    assert np.array_equal(np.load(tmp_path / "a" / "features.npy"), feats[keep])
+    assert np.array_equal(np.load(tmp_path / "a" / "occupancy_gathered.npy"), np.concatenate([gathered[keep], gathered[E + keep]]))
+    assert sum(np.load(tmp_path / "a" / f).nbytes for f in os.listdir(tmp_path / "a")) <= 20000
+    for f in os.listdir(tmp_path / "a"):
+        assert np.array_equal(np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f))
+
+
+def test_steps_below_one_is_refused():
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 2 and "--steps must be at least 1" in r.stderr

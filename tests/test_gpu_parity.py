@@ -453,7 +453,9 @@ def test_power_of_two_scaling_is_exact(built):
 def _run_harness(binary, args, tmp_path, iq, timeout=120):
     import os
     import subprocess
-    exe = os.path.join(os.path.dirname(os.path.abspath(__file__)), "harness", binary)
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    # the binaries built from the reference tree (oracle/Makefile) sit with its other object code in oracle/_ref
+    exe = os.path.join(root, "oracle", "_ref", binary) if binary.endswith("_refbase") else os.path.join(root, "tests", "harness", binary)
     if not os.path.exists(exe):
         pytest.skip(f"{binary} was not built (reference tree absent at build time)")
     path = tmp_path / "iq.bin"
@@ -482,7 +484,7 @@ def test_engine_drop_in_matches_reference_epoch(built, binary, mode, tmp_path):
     the ECR's rx/CE workers do, against the literal reference epoch of the oracle: same decisions,
     same set_tx_freq arguments, same first-call configuration sequence.  The `_refbase` binary is
     the same engine compiled against the reference's own cognitive_engine.hpp and linked with the
-    reference's own CognitiveEngine object code (built where /root/reference is mounted)."""
+    reference's own CognitiveEngine object code (oracle/_ref, built where the reference tree is mounted)."""
     cfg = cs.cfg_reference()
     L, n_epochs = 364, 12
     iq, picks = signals.make_epochs(cfg, n_epochs, seed=4242, L=L)

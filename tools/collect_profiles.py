@@ -22,11 +22,11 @@ for src, dst in (("stats/runc/*_kernel_stats.csv", f"{tag}_kernel_stats.csv"), (
                  ("ring_rate.txt", f"{tag}_ring_rate_round.txt"),
                  ("bench_strong_share_per_gpu.jsonl", f"{tag}_bench_strong_share_per_gpu.jsonl"),
                  ("bench_strong_share_per_gpu_one_stream.jsonl", f"{tag}_bench_strong_share_per_gpu_one_stream.jsonl"),
-                 ("bench_8ranks_one_gpu_strong.json", f"{tag}_bench_eight_self_launched_ranks_one_gpu_stand_in_wire_strong.json"),
+                 ("bench_4ranks_one_gpu_strong.json", f"{tag}_bench_four_self_launched_ranks_one_gpu_stand_in_wire_strong.json"),
                  ("decision_band.txt", f"{tag}_decision_band.txt"),
                  ("bench_driver_shape.json", f"{tag}_bench_driver_shape.json"),
-                 ("bench_8ranks_one_gpu.json", f"{tag}_bench_eight_self_launched_ranks_one_gpu_stand_in_wire.json"),
-                 ("bench_8ranks_one_gpu_scan.json", f"{tag}_bench_cfg4_eight_self_launched_ranks_one_gpu_stand_in_wire.json"),
+                 ("bench_4ranks_one_gpu.json", f"{tag}_bench_four_self_launched_ranks_one_gpu_stand_in_wire.json"),
+                 ("bench_4ranks_one_gpu_scan.json", f"{tag}_bench_cfg4_four_self_launched_ranks_one_gpu_stand_in_wire.json"),
                  ("welch_spans.txt", f"{tag}_welch_spans.txt"), ("soak.txt", f"{tag}_soak_round.txt"),
                  ("dealt_frames_ab.txt", f"{tag}_dealt_frames_ab.txt"), ("engine_idle_gap.txt", f"{tag}_engine_idle_gap.txt"),
                  ("per_bin_error_vs_snr.txt", f"{tag}_per_bin_error_vs_snr.txt"),

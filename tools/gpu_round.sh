@@ -1,5 +1,5 @@
 #!/bin/bash
-# Round evidence (tag $TAG, default r05), one gpurun call, one box: GPU tests, smoke, every bench line (single GPU; N = 8 rehearsed in
+# Round evidence (tag $TAG, default r05), one command on one GPU box: GPU tests, smoke, every bench line (single GPU; N = 4 rehearsed in
 # both scaling modes over the stand-in RCCL), rocprofv3 kernel stats of the headline command, HBM traffic counters (separate --pmc
 # passes per workload), SQ / GRBM counter groups, the engine's execute() latency, host-buffer (PCIe-inclusive) rate, probes.
 #   gpurun --timeout 3600 -- 'bash tools/gpu_round.sh'   then   python tools/collect_profiles.py r05
@@ -28,14 +28,14 @@ timeout 300 python bench.py --fft 2048 --cpu-epochs 0 > $O/bench_e2048.json 2> $
 timeout 600 python3 bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_driver_shape.json 2> $O/bench_driver_shape.err
 { for n in 1 2 4 8; do timeout 300 python bench.py --steps 40 --warmup 10 --cpu-epochs 0 --no-alt --no-live-traffic --epochs $((28672 / n)) $([ $n -gt 2 ] && echo --two-streams) 2>/dev/null | tail -1; done; } > $O/bench_strong_share_per_gpu.jsonl
 { for n in 4 8; do timeout 300 python bench.py --steps 40 --warmup 10 --cpu-epochs 0 --no-alt --no-live-traffic --epochs $((28672 / n)) 2>/dev/null | tail -1; done; } > $O/bench_strong_share_per_gpu_one_stream.jsonl
-# BASELINE.json configs[4] rehearsed the way the driver starts it (no launcher: bench.py starts its own ranks), eight ranks sharing this
-# box's one GPU over the stand-in RCCL (real RCCL refuses two ranks per device), weak and strong scaling
+# BASELINE.json configs[4] rehearsed the way the driver starts it (no launcher: bench.py starts its own ranks), four ranks sharing this
+# box's one GPU over the stand-in RCCL (real RCCL refuses two ranks per device; at most six processes may hold one GPU), weak and strong scaling
 export CRN_RCCL_LIB=$R/tests/harness/libfake_rccl_mp.so HIP_VISIBLE_DEVICES=0
 # (the N > 1 lines carry cpu_baseline: rank 0 measures it after the timed region with the default protocol)
 timeout 900 python3 bench.py --gpus 2 --steps 20 --warmup 5 --epochs 14336 > $O/bench_2ranks_one_gpu.json 2> $O/bench_2ranks_one_gpu.err
-timeout 900 python3 bench.py --gpus 8 --steps 20 --warmup 5 --epochs 3584 > $O/bench_8ranks_one_gpu.json 2> $O/bench_8ranks_one_gpu.err
-timeout 900 python3 bench.py --gpus 8 --steps 20 --warmup 5 --scaling strong > $O/bench_8ranks_one_gpu_strong.json 2> $O/bench_8ranks_one_gpu_strong.err
-timeout 900 python3 bench.py --gpus 8 --steps 20 --warmup 5 --mode scan --epochs 8960 > $O/bench_8ranks_one_gpu_scan.json 2> $O/bench_8ranks_one_gpu_scan.err
+timeout 900 python3 bench.py --gpus 4 --steps 20 --warmup 5 --epochs 7168 > $O/bench_4ranks_one_gpu.json 2> $O/bench_4ranks_one_gpu.err
+timeout 900 python3 bench.py --gpus 4 --steps 20 --warmup 5 --scaling strong > $O/bench_4ranks_one_gpu_strong.json 2> $O/bench_4ranks_one_gpu_strong.err
+timeout 900 python3 bench.py --gpus 4 --steps 20 --warmup 5 --mode scan --epochs 17920 > $O/bench_4ranks_one_gpu_scan.json 2> $O/bench_4ranks_one_gpu_scan.err
 unset CRN_RCCL_LIB HIP_VISIBLE_DEVICES
 timeout 900 python tools/gpu_welch_spans.py > $O/welch_spans.txt 2>&1
 timeout 900 python tests/soak_gpu.py 20000 > $O/soak.txt 2>&1
