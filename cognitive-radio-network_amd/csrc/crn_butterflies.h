@@ -33,59 +33,68 @@ typedef float cx __attribute__((ext_vector_type(2)));
 #define CRN_S1 0.38268343236508977f  // sin(pi/8)
 #define CRN_H_ 0.70710678118654752f  // sqrt(1/2)
 
+// The packed-f32 forms, each spelled once.  A form is the template of ONE inline-asm statement (%0 = destination), so the LLVM
+// hazard recogniser sees a statement boundary after every instruction; csrc/strip_asm_nops.py drops the wait states it puts there
+// (why the statements are not simply grouped: profiles/r07_grouped_butterflies_prototype.txt).
+#define CRN_PK_ADD "v_pk_add_f32 %0, %1, %2"                                                     // a + b
+#define CRN_PK_SUB "v_pk_add_f32 %0, %1, %2 neg_lo:[0,1] neg_hi:[0,1]"                           // a - b
+#define CRN_PK_ADD_MJ "v_pk_add_f32 %0, %1, %2 op_sel:[0,1] op_sel_hi:[1,0] neg_hi:[0,1]"        // a + (-j) b = (a.x + b.y, a.y - b.x)
+#define CRN_PK_SUB_MJ "v_pk_add_f32 %0, %1, %2 op_sel:[0,1] op_sel_hi:[1,0] neg_lo:[0,1]"        // a - (-j) b = (a.x - b.y, a.y + b.x)
+#define CRN_PK_MUL_T "v_pk_mul_f32 %0, %1, %2 op_sel_hi:[1,0]"                                   // t = (a.x w.x, a.y w.x)
+#define CRN_PK_MUL_D "v_pk_fma_f32 %0, %1, %2, %3 op_sel:[1,1,0] op_sel_hi:[0,1,1] neg_lo:[1,0,0]" // a * w = (-a.y w.y + t.x, a.x w.y + t.y)
+#define CRN_PK_MULCONJ_D "v_pk_fma_f32 %0, %1, %2, %3 op_sel:[1,1,0] op_sel_hi:[0,1,1] neg_hi:[1,0,0]" // a * conj(w) = (a.y w.y + t.x, -a.x w.y + t.y)
+// (u, h, x) with h = (CRN_H_, CRN_H_) in SGPRs: neg_* on source 1 flips the sign of h for one or both halves
+#define CRN_PK_FMA_H "v_pk_fma_f32 %0, %1, %2, %3"                                               // x + h u
+#define CRN_PK_FMS_H "v_pk_fma_f32 %0, %1, %2, %3 neg_lo:[0,1,0] neg_hi:[0,1,0]"                 // x - h u
+#define CRN_PK_FMA_H_MJ "v_pk_fma_f32 %0, %1, %2, %3 op_sel:[1,0,0] op_sel_hi:[0,1,1] neg_hi:[0,1,0]" // x + (-j) h u = (x.x + h u.y, x.y - h u.x)
+#define CRN_PK_FMS_H_MJ "v_pk_fma_f32 %0, %1, %2, %3 op_sel:[1,0,0] op_sel_hi:[0,1,1] neg_lo:[0,1,0]" // x - (-j) h u = (x.x - h u.y, x.y + h u.x)
+// (wp, t, x): w_S t + x, w_S = half S of wp (op_sel picks it for both halves); CRN_PK_NEG_X appended: w_S t - x
+#define CRN_PK_FMA_W0 "v_pk_fma_f32 %0, %1, %2, %3 op_sel:[0,0,0] op_sel_hi:[0,1,1]"
+#define CRN_PK_FMA_W1 "v_pk_fma_f32 %0, %1, %2, %3 op_sel:[1,0,0] op_sel_hi:[1,1,1]"
+#define CRN_PK_NEG_X " neg_lo:[0,0,1] neg_hi:[0,0,1]"
+
 template <bool PK>
 struct M {
   CRN_HD cx add(cx a, cx b) {
-    if constexpr (PK) { cx d; asm("v_pk_add_f32 %0, %1, %2" : "=v"(d) : "v"(a), "v"(b)); return d; }
+    if constexpr (PK) { cx d; asm(CRN_PK_ADD : "=v"(d) : "v"(a), "v"(b)); return d; }
     else return cx{a.x + b.x, a.y + b.y};
   }
   CRN_HD cx sub(cx a, cx b) {
-    if constexpr (PK) { cx d; asm("v_pk_add_f32 %0, %1, %2 neg_lo:[0,1] neg_hi:[0,1]" : "=v"(d) : "v"(a), "v"(b)); return d; }
+    if constexpr (PK) { cx d; asm(CRN_PK_SUB : "=v"(d) : "v"(a), "v"(b)); return d; }
     else return cx{a.x - b.x, a.y - b.y};
   }
-  // a + (-j) b = (a.x + b.y, a.y - b.x)
   CRN_HD cx add_mj(cx a, cx b) {
-    if constexpr (PK) { cx d; asm("v_pk_add_f32 %0, %1, %2 op_sel:[0,1] op_sel_hi:[1,0] neg_hi:[0,1]" : "=v"(d) : "v"(a), "v"(b)); return d; }
+    if constexpr (PK) { cx d; asm(CRN_PK_ADD_MJ : "=v"(d) : "v"(a), "v"(b)); return d; }
     else return cx{a.x + b.y, a.y - b.x};
   }
-  // a - (-j) b = (a.x - b.y, a.y + b.x)
   CRN_HD cx sub_mj(cx a, cx b) {
-    if constexpr (PK) { cx d; asm("v_pk_add_f32 %0, %1, %2 op_sel:[0,1] op_sel_hi:[1,0] neg_lo:[0,1]" : "=v"(d) : "v"(a), "v"(b)); return d; }
+    if constexpr (PK) { cx d; asm(CRN_PK_SUB_MJ : "=v"(d) : "v"(a), "v"(b)); return d; }
     else return cx{a.x - b.y, a.y + b.x};
   }
   // a * w, w in VGPRs (per-lane twiddle)
   CRN_HD cx mul(cx a, cx w) {
-    if constexpr (PK) {
-      cx t, d;
-      asm("v_pk_mul_f32 %0, %1, %2 op_sel_hi:[1,0]" : "=v"(t) : "v"(a), "v"(w));  // (a.x w.x, a.y w.x)
-      asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[1,1,0] op_sel_hi:[0,1,1] neg_lo:[1,0,0]"
-          : "=v"(d) : "v"(a), "v"(w), "v"(t));                                     // (-a.y w.y + t.x, a.x w.y + t.y)
-      return d;
-    } else {
-      return cx{fmaf(-a.y, w.y, a.x * w.x), fmaf(a.y, w.x, a.x * w.y)};
-    }
+    if constexpr (PK) { cx t, d; asm(CRN_PK_MUL_T : "=v"(t) : "v"(a), "v"(w)); asm(CRN_PK_MUL_D : "=v"(d) : "v"(a), "v"(w), "v"(t)); return d; }
+    else return cx{fmaf(-a.y, w.y, a.x * w.x), fmaf(a.y, w.x, a.x * w.y)};
   }
   // a * conj(w) = (a.x w.x + a.y w.y, a.y w.x - a.x w.y)
   CRN_HD cx mul_conj(cx a, cx w) {
-    if constexpr (PK) {
-      cx t, d;
-      asm("v_pk_mul_f32 %0, %1, %2 op_sel_hi:[1,0]" : "=v"(t) : "v"(a), "v"(w));
-      asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[1,1,0] op_sel_hi:[0,1,1] neg_hi:[1,0,0]"
-          : "=v"(d) : "v"(a), "v"(w), "v"(t));
-      return d;
-    } else {
-      return cx{fmaf(a.y, w.y, a.x * w.x), fmaf(-a.x, w.y, a.y * w.x)};
-    }
+    if constexpr (PK) { cx t, d; asm(CRN_PK_MUL_T : "=v"(t) : "v"(a), "v"(w)); asm(CRN_PK_MULCONJ_D : "=v"(d) : "v"(a), "v"(w), "v"(t)); return d; }
+    else return cx{fmaf(a.y, w.y, a.x * w.x), fmaf(-a.x, w.y, a.y * w.x)};
+  }
+  // a * w, w a wave-uniform constant held in an SGPR pair
+  CRN_HD cx mul_c(cx a, cx w) {
+    if constexpr (PK) { cx t, d; asm(CRN_PK_MUL_T : "=v"(t) : "v"(a), "s"(w)); asm(CRN_PK_MUL_D : "=v"(d) : "v"(a), "s"(w), "v"(t)); return d; }
+    else return cx{fmaf(-a.y, w.y, a.x * w.x), fmaf(a.y, w.x, a.x * w.y)};
   }
   // w_S * t + x (NEG: w_S * t - x), w_S = half S of the register pair wp: a real weight applied to a complex value
   template <int S, bool NEG>
   CRN_HD cx fma_w(cx wp, cx t, cx x) {
     if constexpr (PK) {
       cx d;
-      if constexpr (S == 0 && !NEG) asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[0,0,0] op_sel_hi:[0,1,1]" : "=v"(d) : "v"(wp), "v"(t), "v"(x));
-      if constexpr (S == 1 && !NEG) asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[1,0,0] op_sel_hi:[1,1,1]" : "=v"(d) : "v"(wp), "v"(t), "v"(x));
-      if constexpr (S == 0 && NEG) asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[0,0,0] op_sel_hi:[0,1,1] neg_lo:[0,0,1] neg_hi:[0,0,1]" : "=v"(d) : "v"(wp), "v"(t), "v"(x));
-      if constexpr (S == 1 && NEG) asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[1,0,0] op_sel_hi:[1,1,1] neg_lo:[0,0,1] neg_hi:[0,0,1]" : "=v"(d) : "v"(wp), "v"(t), "v"(x));
+      if constexpr (S == 0 && !NEG) asm(CRN_PK_FMA_W0 : "=v"(d) : "v"(wp), "v"(t), "v"(x));
+      if constexpr (S == 1 && !NEG) asm(CRN_PK_FMA_W1 : "=v"(d) : "v"(wp), "v"(t), "v"(x));
+      if constexpr (S == 0 && NEG) asm(CRN_PK_FMA_W0 CRN_PK_NEG_X : "=v"(d) : "v"(wp), "v"(t), "v"(x));
+      if constexpr (S == 1 && NEG) asm(CRN_PK_FMA_W1 CRN_PK_NEG_X : "=v"(d) : "v"(wp), "v"(t), "v"(x));
       return d;
     } else {
       const float w = S == 0 ? wp.x : wp.y;
@@ -93,46 +102,25 @@ struct M {
     }
   }
   // The twiddles W16^2 = sqrt(1/2) (1 - j), W16^6 = -sqrt(1/2) (1 + j) (and W8^1, W8^3) are not multiplied out: (1 -+ j) a is one
-  // packed add of a with itself rotated (add_mj / sub_mj below), and the factor h = sqrt(1/2) rides in the FMA that consumes the
+  // packed add of a with itself rotated (add_mj / sub_mj), and the factor h = sqrt(1/2) rides in the FMA that consumes the
   // product — x +- h u instead of x +- (u * w): one packed add + the FMA where a complex multiply (two packed instructions, four
   // real multiplies) + an add stood.  4 packed instructions fewer per 16-point transform, 12 of the ~334 of a 4096-point frame.
   //   fma_h(u, x) = x + h u      fms_h(u, x) = x - h u      fma_h_mj(u, x) = x + (-j) h u      fms_h_mj(u, x) = x - (-j) h u
-  // (h comes as an SGPR pair (h, h); neg_* on source 1 flips the sign of h for one or both halves)
   CRN_HD cx fma_h(cx u, cx x) {
-    if constexpr (PK) { cx d; const cx h = {CRN_H_, CRN_H_}; asm("v_pk_fma_f32 %0, %1, %2, %3" : "=v"(d) : "v"(u), "s"(h), "v"(x)); return d; }
+    if constexpr (PK) { cx d; const cx h = {CRN_H_, CRN_H_}; asm(CRN_PK_FMA_H : "=v"(d) : "v"(u), "s"(h), "v"(x)); return d; }
     else return cx{fmaf(CRN_H_, u.x, x.x), fmaf(CRN_H_, u.y, x.y)};
   }
   CRN_HD cx fms_h(cx u, cx x) {
-    if constexpr (PK) { cx d; const cx h = {CRN_H_, CRN_H_}; asm("v_pk_fma_f32 %0, %1, %2, %3 neg_lo:[0,1,0] neg_hi:[0,1,0]" : "=v"(d) : "v"(u), "s"(h), "v"(x)); return d; }
+    if constexpr (PK) { cx d; const cx h = {CRN_H_, CRN_H_}; asm(CRN_PK_FMS_H : "=v"(d) : "v"(u), "s"(h), "v"(x)); return d; }
     else return cx{fmaf(-CRN_H_, u.x, x.x), fmaf(-CRN_H_, u.y, x.y)};
   }
-  // x + (-j) h u = (x.x + h u.y, x.y - h u.x)
   CRN_HD cx fma_h_mj(cx u, cx x) {
-    if constexpr (PK) {
-      cx d; const cx h = {CRN_H_, CRN_H_};
-      asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[1,0,0] op_sel_hi:[0,1,1] neg_hi:[0,1,0]" : "=v"(d) : "v"(u), "s"(h), "v"(x));
-      return d;
-    } else return cx{fmaf(CRN_H_, u.y, x.x), fmaf(-CRN_H_, u.x, x.y)};
+    if constexpr (PK) { cx d; const cx h = {CRN_H_, CRN_H_}; asm(CRN_PK_FMA_H_MJ : "=v"(d) : "v"(u), "s"(h), "v"(x)); return d; }
+    else return cx{fmaf(CRN_H_, u.y, x.x), fmaf(-CRN_H_, u.x, x.y)};
   }
-  // x - (-j) h u = (x.x - h u.y, x.y + h u.x)
   CRN_HD cx fms_h_mj(cx u, cx x) {
-    if constexpr (PK) {
-      cx d; const cx h = {CRN_H_, CRN_H_};
-      asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[1,0,0] op_sel_hi:[0,1,1] neg_lo:[0,1,0]" : "=v"(d) : "v"(u), "s"(h), "v"(x));
-      return d;
-    } else return cx{fmaf(-CRN_H_, u.y, x.x), fmaf(CRN_H_, u.x, x.y)};
-  }
-  // a * w, w a wave-uniform constant held in an SGPR pair
-  CRN_HD cx mul_c(cx a, cx w) {
-    if constexpr (PK) {
-      cx t, d;
-      asm("v_pk_mul_f32 %0, %1, %2 op_sel_hi:[1,0]" : "=v"(t) : "v"(a), "s"(w));
-      asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[1,1,0] op_sel_hi:[0,1,1] neg_lo:[1,0,0]"
-          : "=v"(d) : "v"(a), "s"(w), "v"(t));
-      return d;
-    } else {
-      return cx{fmaf(-a.y, w.y, a.x * w.x), fmaf(a.y, w.x, a.x * w.y)};
-    }
+    if constexpr (PK) { cx d; const cx h = {CRN_H_, CRN_H_}; asm(CRN_PK_FMS_H_MJ : "=v"(d) : "v"(u), "s"(h), "v"(x)); return d; }
+    else return cx{fmaf(-CRN_H_, u.y, x.x), fmaf(CRN_H_, u.x, x.y)};
   }
 };
 
