@@ -208,6 +208,42 @@ CRN_API int crn_sense_run_device(crn_handle *h, const float *d_iq, int64_t n_epo
 CRN_API int crn_sense_run_host(crn_handle *h, const float *iq, int64_t n_epochs,
                        int32_t samples_per_frame, int64_t epoch_stride, const crn_out *out);
 
+/* -- per-bin CA-CFAR detection (cell averaging, constant false-alarm rate) --------------------------------------------------
+ * A handle created with mode CRN_MODE_ENERGY and decide CRN_DECIDE_THRESHOLD or CRN_DECIDE_NONE can decide per bin instead of per
+ * fixed band.  With P[k] the K-frame mean energy of bin k (the `spectrum` output), guard cells g and training cells W on each side:
+ *   Z[k] = (1 / 2W) sum P[(k + i) mod N] over g < |i| <= g + W   (circular: bin N-1 neighbours bin 0)
+ *   bin k detected  <=>  P[k] > alpha * Z[k]   (fp32)
+ *   band_bins[b] = detected bins in band b's segments (a bin counts once per segment listing, as the band sums count it)
+ *   occupancy[b] = band_bins[b] >= min_bins,  decision = number of occupied bands
+ * `features` stay the band energy sums and `spectrum` the per-bin means; the stored thresholds are kept but not used while CFAR is on.
+ * The threshold follows the local noise floor (filter roll-off, a DC spike), so no calibration is needed.
+ * Parameters: 1 <= train <= 64, guard >= 0, 2 (guard + train) + 1 <= fft_len, alpha > 0 and finite, min_bins >= 1, reserved = 0.
+ * Suggested (not applied automatically): guard 2, train 16, alpha from crn_cfar_alpha(1e-3, frames_per_epoch, 16, &alpha),
+ * min_bins 1.  All windows, hop == fft_len or fft_len / 2, and every fft_len are supported. */
+typedef struct crn_cfar_params {
+  int32_t guard, train, min_bins, reserved;
+  float alpha;
+} crn_cfar_params;
+
+/* Switch CFAR on with `params`, or back to the cfg's own rule with NULL; launches enqueued after the call use the new values.
+ * CRN_ERR_ARG on a REF_MAG handle or for parameters out of range; CRN_ERR_STATE on an ANN handle or while an ingest ring is attached.
+ * Not supported yet (CRN_ERR_ARG): an ingest ring on a CFAR handle (crn_epoch_result has no room for the mask) and wire-format (sc16)
+ * launches. */
+CRN_API int crn_sense_set_cfar(crn_handle *h, const crn_cfar_params *params);
+/* The parameters in force and whether CFAR is on (*on = 0: params holds the last ones set, zeros if none).  Either pointer may be NULL. */
+CRN_API int crn_sense_get_cfar(crn_handle *h, crn_cfar_params *params, int32_t *on);
+/* crn_sense_run_device with the CFAR outputs (device pointers, either may be NULL):
+ *   d_bin_mask   [n_epochs][fft_len / 32] bit k % 32 of word k / 32 = bin k detected
+ *   d_band_bins  [n_epochs][n_bands]      detected bins per band
+ * CRN_ERR_STATE when CFAR is off.  (crn_sense_run_device on a CFAR handle gives the CFAR occupancy and decision without these two.) */
+CRN_API int crn_sense_run_device_cfar(crn_handle *h, const float *d_iq, int64_t n_epochs, int32_t samples_per_frame, int64_t epoch_stride,
+                                      const crn_out *d_out, uint32_t *d_bin_mask, int32_t *d_band_bins, void *stream);
+/* alpha for a false-alarm probability `pfa` per bin (0 < pfa < 1), frames_per_epoch K >= 1 and train W (1..64), host only.
+ * Assumes white complex Gaussian noise, the rectangular window and disjoint frames: P[k] / Z[k] then follows F(2K, 4WK), and
+ * pfa = P(F > alpha) is inverted by bisection on the regularised incomplete beta function (K = 1: pfa = (1 + alpha / 2W)^(-2W)).
+ * Windowed or overlapped frames correlate neighbouring bins and frames: the real false-alarm rate then differs from `pfa`. */
+CRN_API int crn_cfar_alpha(double pfa, int32_t frames_per_epoch, int32_t train, double *alpha);
+
 /* Allocate, now, the device scratch and pinned staging that crn_sense_run_host needs for up to
  * max_epochs dense epochs of full-length frames (and their per-bin spectra when want_spectrum != 0),
  * and load the kernels: a later crn_sense_run_host within that size allocates nothing.  An engine

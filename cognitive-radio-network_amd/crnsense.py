@@ -44,6 +44,7 @@ EXPORTS = [
     "crn_ingest_calibrate", "crn_ingest_noise_floor",
     "crn_sense_reserve_host", "crn_sense_set_timing", "crn_sense_get_stats", "crn_ingest_get_stats",
     "crn_monitor_rows_device",
+    "crn_sense_set_cfar", "crn_sense_get_cfar", "crn_sense_run_device_cfar", "crn_cfar_alpha",
     "crn_comm_unique_id", "crn_comm_create", "crn_comm_local", "crn_comm_allgather", "crn_comm_gathered",
     "crn_comm_finish", "crn_comm_destroy", "crn_comm_local_addr", "crn_comm_wait", "crn_comm_info",
     "crn_last_error", "crn_abi_version", "crn_build_info",
@@ -72,6 +73,11 @@ class Cfg(C.Structure):
 class Out(C.Structure):
     _fields_ = [("features", C.c_void_p), ("ann_out", C.c_void_p), ("decision", C.c_void_p),
                 ("occupancy", C.c_void_p), ("spectrum", C.c_void_p)]
+
+
+class CfarParams(C.Structure):
+    """crn_cfar_params: per-bin CA-CFAR (crn_sense_set_cfar)."""
+    _fields_ = [("guard", C.c_int32), ("train", C.c_int32), ("min_bins", C.c_int32), ("reserved", C.c_int32), ("alpha", C.c_float)]
 
 
 class EpochResult(C.Structure):
@@ -177,6 +183,11 @@ def lib():
         L.crn_sense_kernel_info.argtypes = [C.c_void_p, C.c_char_p, C.c_int32, C.POINTER(C.c_int32),
                                             C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
         L.crn_sense_set_variant.argtypes = [C.c_void_p, C.c_int32]
+        L.crn_sense_set_cfar.argtypes = [C.c_void_p, C.POINTER(CfarParams)]
+        L.crn_sense_get_cfar.argtypes = [C.c_void_p, C.POINTER(CfarParams), C.POINTER(C.c_int32)]
+        L.crn_sense_run_device_cfar.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.POINTER(Out),
+                                                C.c_void_p, C.c_void_p, C.c_void_p]
+        L.crn_cfar_alpha.argtypes = [C.c_double, C.c_int32, C.c_int32, C.POINTER(C.c_double)]
         L.crn_ingest_create.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]
         L.crn_ingest_push.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
         L.crn_ingest_flush.argtypes = [C.c_void_p]
@@ -263,6 +274,14 @@ def cfg_welch_scaled(fft_len, frames_per_epoch=8, lam=4.0):
     c = Cfg()
     check(lib().crn_cfg_welch_scaled(C.byref(c), fft_len, frames_per_epoch, lam), "crn_cfg_welch_scaled")
     return c
+
+
+def cfar_alpha(pfa, K, train):
+    """CFAR scale alpha for a per-bin false-alarm probability pfa at K frames per epoch and `train` training cells per side
+    (white complex Gaussian noise, rectangular window, disjoint frames: include/crn_sense.h, crn_cfar_alpha)."""
+    a = C.c_double()
+    check(lib().crn_cfar_alpha(float(pfa), int(K), int(train), C.byref(a)), "crn_cfar_alpha")
+    return a.value
 
 
 def save_ann(cfg, path):
@@ -410,6 +429,29 @@ class Sensor:
         fn = lib().crn_sense_run_device_sc16 if sc16 else lib().crn_sense_run_device
         check(fn(self._h, iq_ptr, n_epochs, L, epoch_stride, C.byref(o), C.c_void_p(stream or None)),
               "crn_sense_run_device_sc16" if sc16 else "crn_sense_run_device")
+
+    def set_cfar(self, guard, train=16, alpha=None, min_bins=1):
+        """Per-bin CA-CFAR on (guard, train, alpha, min_bins), or off with set_cfar(None).  alpha defaults to cfar_alpha(1e-3, K, train)."""
+        if guard is None:
+            check(lib().crn_sense_set_cfar(self._h, None), "crn_sense_set_cfar")
+            return
+        if alpha is None:
+            alpha = cfar_alpha(1e-3, self.cfg.frames_per_epoch, train)
+        q = CfarParams(guard=int(guard), train=int(train), min_bins=int(min_bins), reserved=0, alpha=float(alpha))
+        check(lib().crn_sense_set_cfar(self._h, C.byref(q)), "crn_sense_set_cfar")
+
+    def get_cfar(self):
+        """None while CFAR is off, else {"guard", "train", "alpha", "min_bins"}."""
+        q, on = CfarParams(), C.c_int32()
+        check(lib().crn_sense_get_cfar(self._h, C.byref(q), C.byref(on)), "crn_sense_get_cfar")
+        return {"guard": q.guard, "train": q.train, "alpha": q.alpha, "min_bins": q.min_bins} if on.value else None
+
+    def run_device_cfar(self, iq_ptr, n_epochs, L, out_ptrs, mask_ptr=0, band_bins_ptr=0, stream=0, epoch_stride=0):
+        """run_device plus the CFAR outputs: mask_ptr [n_epochs][fft_len / 32] uint32, band_bins_ptr [n_epochs][n_bands] int32 (device
+        addresses, 0 = not wanted)."""
+        o = Out(**{k: (v or None) for k, v in out_ptrs.items()})
+        check(lib().crn_sense_run_device_cfar(self._h, iq_ptr, n_epochs, L, epoch_stride, C.byref(o), C.c_void_p(mask_ptr or None),
+                                              C.c_void_p(band_bins_ptr or None), C.c_void_p(stream or None)), "crn_sense_run_device_cfar")
 
     def set_wire_full_scale(self, full_scale):
         _need_sc16("set_wire_full_scale")

@@ -50,6 +50,8 @@ struct crn_handle {
   int n_cus = 256;              // compute units of the device (workgroup slots = n_cus x workgroups per CU): read at creation
   size_t lds_budget = 64 * 1024;   // LDS a workgroup may ask for on this device (hipDeviceAttributeMaxSharedMemoryPerBlock: 160 KiB on gfx950)
   unsigned acc_mask = 0xFFFFu;  // accumulator registers (bit j R3 + d) that hold a bin of some band (N = 4096: the 256-bin rows)
+  bool cfar_on = false;         // crn_sense_set_cfar: per-bin CA-CFAR decides instead of the cfg's rule (under tables_mu)
+  crn_cfar_params cfar{};       // the parameters last set
   // one device slab holding every table
   void *d_tables = nullptr;
   const float2 *d_tw1 = nullptr, *d_tw2 = nullptr;
@@ -388,6 +390,14 @@ int crn_sense_destroy(crn_handle *h) {
 // internal (crn_ingest.cpp): a ring attaches to / detaches from its handle
 int crn_sense_ring_count(crn_handle *h, int delta) {
   if (!h) return crn::fail(CRN_ERR_ARG, "null handle");
+  if (delta > 0) {   // attaching: refused on a CFAR handle, checked and claimed under the lock crn_sense_set_cfar holds
+    std::lock_guard<std::mutex> lk(h->tables_mu);
+    if (h->cfar_on)
+      return crn::fail(CRN_ERR_ARG, "crn_ingest_create: a ring on a CFAR handle is not supported yet (crn_epoch_result has no room for "
+                                    "the bin mask)");
+    h->n_rings.fetch_add(delta, std::memory_order_acq_rel);
+    return CRN_OK;
+  }
   h->n_rings.fetch_add(delta, std::memory_order_acq_rel);
   return CRN_OK;
 }
@@ -479,8 +489,8 @@ int crn_sense_kernel_info(crn_handle *h, char *name, int32_t name_len, int32_t *
     std::snprintf(name, (size_t)name_len, "sense_kernel<R3=%d,NBUF=%d,PREFETCH=%d,NT=%d,TW2LDS=%d,PK=%d,MAG=%d,WIN=%s,CLOSE=%s%s>",
                   h->cfg.fft_len / 256, nbuf, pf, nt, tl, pk,
                   h->cfg.mode == CRN_MODE_REF_MAG, h->cfg.window == CRN_WINDOW_RECT ? "0" : hann_fold ? "hann-in-pass1" : "table",
-                  aligned ? "aligned-bands(dpp)" : reg_close ? "registers" : "lds",
-                  prune_note);
+                  h->cfar_on ? "lds+cfar" : aligned ? "aligned-bands(dpp)" : reg_close ? "registers" : "lds",
+                  h->cfar_on ? "" : prune_note);
   }
   return CRN_OK;
 }
@@ -551,7 +561,8 @@ int crn_sense_get_stats(crn_handle *h, crn_sense_stats *out) {
 }
 
 static int run_device_impl(crn_handle *h, const void *d_iq, int64_t n_epochs, int32_t samples_per_frame,
-                           int64_t epoch_stride, const crn_out *d_out, void *stream, bool sc16) {
+                           int64_t epoch_stride, const crn_out *d_out, void *stream, bool sc16,
+                           uint32_t *d_cfar_mask = nullptr, int32_t *d_cfar_band_bins = nullptr, bool want_cfar = false) {
   if (!h || !d_out) return crn::fail(CRN_ERR_ARG, "null handle / outputs");
   if (n_epochs < 0) return crn::fail(CRN_ERR_ARG, "n_epochs < 0");
   if (n_epochs == 0) return CRN_OK;
@@ -561,6 +572,8 @@ static int run_device_impl(crn_handle *h, const void *d_iq, int64_t n_epochs, in
     return crn::fail(CRN_ERR_ARG, sc16 ? "IQ pointer must be 4-byte aligned" : "IQ pointer must be 8-byte aligned");
   // one plan, whole, from here until the kernel is enqueued (live updates from another thread wait; see crn_handle::tables_mu)
   std::lock_guard<std::mutex> tables_lk(h->tables_mu);
+  if (want_cfar && !h->cfar_on) return crn::fail(CRN_ERR_STATE, "crn_sense_run_device_cfar: CFAR is off on this handle (crn_sense_set_cfar)");
+  if (sc16 && h->cfar_on) return crn::fail(CRN_ERR_ARG, "CFAR on wire-format (sc16) samples is not supported yet");
   int frame_stride = 0;
   if (int rc = resolve_strides(h, samples_per_frame, &epoch_stride, &frame_stride)) return rc;
   if (n_epochs > (int64_t)0x7fffffff) return crn::fail(CRN_ERR_ARG, "n_epochs too large for one launch");
@@ -618,7 +631,8 @@ static int run_device_impl(crn_handle *h, const void *d_iq, int64_t n_epochs, in
     // HBM and 29.4 -> 15.4 from pinned host memory (the ring's launch); 256 epochs 20.3 -> 10.9; from 512 epochs on — two
     // workgroups per CU — the energy forms lose (17.5 -> 20.5), so the switch sits at one per CU.
     const int64_t deal_max = h->deal_max_epochs >= 0 ? h->deal_max_epochs : (int64_t)h->n_cus;
-    if (n_epochs <= deal_max && (h->variant == 0 || h->variant == 13))
+    // (a CFAR handle has no dealt form: the kCfar kernels stream)
+    if (!h->cfar_on && n_epochs <= deal_max && (h->variant == 0 || h->variant == 13))
       p.deal_rounds = crn::sense_deal_rounds(c.fft_len, c.mode == CRN_MODE_REF_MAG, c.window != CRN_WINDOW_RECT,
                                              c.window == CRN_WINDOW_HANN && samples_per_frame == c.fft_len, c.frames_per_epoch, h->lds_budget);
   }
@@ -650,6 +664,15 @@ static int run_device_impl(crn_handle *h, const void *d_iq, int64_t n_epochs, in
   p.decision = d_out->decision;
   p.occupancy = d_out->occupancy;
   p.spectrum = d_out->spectrum;
+  if (h->cfar_on) {
+    p.cfar_on = 1;
+    p.cfar_guard = h->cfar.guard;
+    p.cfar_train = h->cfar.train;
+    p.cfar_min_bins = h->cfar.min_bins;
+    p.cfar_scale = (float)((double)h->cfar.alpha / (2.0 * h->cfar.train));
+    p.cfar_mask = d_cfar_mask;
+    p.cfar_band_bins = d_cfar_band_bins;
+  }
   int slot = -1;
   {
     std::lock_guard<std::mutex> lk(h->timing_mu);
@@ -678,6 +701,96 @@ static int run_device_impl(crn_handle *h, const void *d_iq, int64_t n_epochs, in
 int crn_sense_run_device(crn_handle *h, const float *d_iq, int64_t n_epochs, int32_t samples_per_frame,
                          int64_t epoch_stride, const crn_out *d_out, void *stream) {
   return run_device_impl(h, d_iq, n_epochs, samples_per_frame, epoch_stride, d_out, stream, false);
+}
+
+int crn_sense_run_device_cfar(crn_handle *h, const float *d_iq, int64_t n_epochs, int32_t samples_per_frame, int64_t epoch_stride,
+                              const crn_out *d_out, uint32_t *d_bin_mask, int32_t *d_band_bins, void *stream) {
+  return run_device_impl(h, d_iq, n_epochs, samples_per_frame, epoch_stride, d_out, stream, false, d_bin_mask, d_band_bins, true);
+}
+
+int crn_sense_set_cfar(crn_handle *h, const crn_cfar_params *q) {
+  if (!h) return crn::fail(CRN_ERR_ARG, "null handle");
+  std::lock_guard<std::mutex> lk(h->tables_mu);
+  if (!q) {
+    h->cfar_on = false;
+    return CRN_OK;
+  }
+  const crn_cfg &c = h->cfg;
+  if (c.mode != CRN_MODE_ENERGY) return crn::fail(CRN_ERR_ARG, "crn_sense_set_cfar: CFAR needs mode CRN_MODE_ENERGY");
+  if (c.decide == CRN_DECIDE_ANN) return crn::fail(CRN_ERR_STATE, "crn_sense_set_cfar: not on a DECIDE_ANN handle (THRESHOLD or NONE)");
+  if (h->n_rings.load(std::memory_order_acquire) > 0)
+    return crn::fail(CRN_ERR_STATE, "crn_sense_set_cfar: an ingest ring is attached (CFAR with the ring is not supported yet)");
+  if (q->train < 1 || q->train > 64) return crn::fail(CRN_ERR_ARG, "crn_sense_set_cfar: train must be in 1..64");
+  if (q->guard < 0) return crn::fail(CRN_ERR_ARG, "crn_sense_set_cfar: guard < 0");
+  if (2 * ((int64_t)q->guard + q->train) + 1 > c.fft_len) return crn::fail(CRN_ERR_ARG, "crn_sense_set_cfar: 2 (guard + train) + 1 > fft_len");
+  if (!(q->alpha > 0.f) || !std::isfinite(q->alpha)) return crn::fail(CRN_ERR_ARG, "crn_sense_set_cfar: alpha must be > 0 and finite");
+  if (q->min_bins < 1) return crn::fail(CRN_ERR_ARG, "crn_sense_set_cfar: min_bins < 1");
+  if (q->reserved != 0) return crn::fail(CRN_ERR_ARG, "crn_sense_set_cfar: reserved must be 0");
+  h->cfar = *q;
+  h->cfar_on = true;
+  return CRN_OK;
+}
+
+int crn_sense_get_cfar(crn_handle *h, crn_cfar_params *q, int32_t *on) {
+  if (!h) return crn::fail(CRN_ERR_ARG, "null handle");
+  std::lock_guard<std::mutex> lk(h->tables_mu);
+  if (q) *q = h->cfar;
+  if (on) *on = h->cfar_on ? 1 : 0;
+  return CRN_OK;
+}
+
+namespace {
+// Regularised incomplete beta I_x(a, b) by its continued fraction (modified Lentz), on the side where it converges fast.
+double inc_beta(double a, double b, double x) {
+  if (x <= 0.0) return 0.0;
+  if (x >= 1.0) return 1.0;
+  if (x > (a + 1.0) / (a + b + 2.0)) return 1.0 - inc_beta(b, a, 1.0 - x);
+  const double ln_front = std::lgamma(a + b) - std::lgamma(a) - std::lgamma(b) + a * std::log(x) + b * std::log1p(-x);
+  const double tiny = 1e-300;
+  double c = 1.0, d = 1.0 - (a + b) * x / (a + 1.0);
+  d = std::fabs(d) < tiny ? tiny : d;
+  d = 1.0 / d;
+  double f = d;
+  for (int m = 1; m <= 10000; m++) {
+    for (int odd = 0; odd < 2; odd++) {
+      const double num = odd ? -(a + m) * (a + b + m) * x / ((a + 2.0 * m) * (a + 2.0 * m + 1.0))
+                             : m * (b - m) * x / ((a + 2.0 * m - 1.0) * (a + 2.0 * m));
+      d = 1.0 + num * d;
+      d = std::fabs(d) < tiny ? tiny : d;
+      c = 1.0 + num / c;
+      c = std::fabs(c) < tiny ? tiny : c;
+      d = 1.0 / d;
+      const double step = c * d;
+      f *= step;
+      if (odd && std::fabs(step - 1.0) < 1e-16) return std::exp(ln_front) * f / a;
+    }
+  }
+  return std::exp(ln_front) * f / a;
+}
+// P(F(d1, d2) > alpha) = I_{d2 / (d2 + d1 alpha)}(d2 / 2, d1 / 2)
+double f_tail(double alpha, double d1, double d2) { return inc_beta(0.5 * d2, 0.5 * d1, d2 / (d2 + d1 * alpha)); }
+}  // namespace
+
+int crn_cfar_alpha(double pfa, int32_t frames_per_epoch, int32_t train, double *alpha) {
+  if (!alpha) return crn::fail(CRN_ERR_ARG, "crn_cfar_alpha: null alpha");
+  if (!(pfa > 0.0 && pfa < 1.0)) return crn::fail(CRN_ERR_ARG, "crn_cfar_alpha: pfa must be in (0, 1)");
+  if (frames_per_epoch < 1) return crn::fail(CRN_ERR_ARG, "crn_cfar_alpha: frames_per_epoch < 1");
+  if (train < 1 || train > 64) return crn::fail(CRN_ERR_ARG, "crn_cfar_alpha: train must be in 1..64");
+  const double d1 = 2.0 * frames_per_epoch, d2 = 4.0 * train * frames_per_epoch;
+  // the tail falls monotonically from 1 at alpha = 0: bracket, then bisect to the last bit
+  double lo = 0.0, hi = 1.0;
+  while (f_tail(hi, d1, d2) > pfa) {
+    lo = hi;
+    hi *= 2.0;
+    if (hi > 1e300) return crn::fail(CRN_ERR_ARG, "crn_cfar_alpha: pfa too small");
+  }
+  for (int i = 0; i < 2000 && hi - lo > 1e-16 * hi; i++) {
+    const double mid = 0.5 * (lo + hi);
+    if (mid <= lo || mid >= hi) break;
+    (f_tail(mid, d1, d2) > pfa ? lo : hi) = mid;
+  }
+  *alpha = 0.5 * (lo + hi);
+  return CRN_OK;
 }
 
 // internal (crn_ingest.cpp): either sample format through one call — a ring of wire-format packets (bytes_per_sample 4) exists only

@@ -35,6 +35,8 @@ constexpr int kCloseLdsBytes = kBandTabWords * 4 + 8 * 16 * 4;
 typedef __attribute__((address_space(3))) float lds_f32;
 typedef __attribute__((address_space(3))) int lds_i32;
 typedef __attribute__((address_space(3))) double lds_f64;
+typedef __attribute__((address_space(3))) unsigned short lds_u16;
+typedef __attribute__((address_space(3))) unsigned int lds_u32;
 CRN_DEV unsigned lds_offset(const void *p) {
   return (unsigned)(unsigned long long)(__attribute__((address_space(3))) const void *)p;
 }
@@ -180,6 +182,7 @@ CRN_DEV void epoch_close(FrameCtx<C> &c, const SenseParams &p, long long epoch_b
   lds_f32 *part = reinterpret_cast<lds_f32 *>(tab_off + kBandTabWords * 4);  // [256 / TEAM][16]
   [[maybe_unused]] const lds_f32 *feat = nullptr;
   // Three forms of the close, chosen per launch (one kernel holding several spilled in the frame loop):
+  static_assert((C::OPT & kCfar) == 0 || (C::OPT & (kAlignedBands | kRegBands | kRows | kDeal)) == 0, "CFAR runs in the LDS form of the close");
   if constexpr ((C::OPT & kAlignedBands) != 0) {
     // Equal contiguous bands of W = 2^sh bins, sh = 6..8 (the Welch scan's 64 channels of 64 bins), N = 4096:
     // thread (a, m_lo) holds bins 256 d + 16 m_lo + a in acc[d], so band (256 d + 16 m_lo) >> sh is the sum over
@@ -441,12 +444,113 @@ CRN_DEV void epoch_close(FrameCtx<C> &c, const SenseParams &p, long long epoch_b
 
     feat = featl;
 
+    // CA-CFAR (kCfar): bin k is detected when P[k] > alpha Z[k], Z[k] the mean of the 2 W training cells g < |i| <= g + W around it,
+    // circular over the N bins.  Both sides carry the same 1 / K, so the test runs on the K-frame sums in the image:
+    // x[k] > s T(k), T(k) the sum of the 2 W training cells, s = alpha / 2 W rounded once to fp32 on the host.  Thread t owns bins
+    // 16 t .. 16 t + 15 (the band sums' blocks).  A window sum must never be formed by subtracting a cell that left it: a strong bin
+    // that enters and leaves a sliding fp32 sum leaves ~ulp32(strong bin) behind, 30-50 % of the training sum at 80-90 dB over the floor.
+    //   W >= 16: with y[i] = x[16 t - g - W + i] (left) and z[i] = x[16 t + g + 1 + i] (right), bin 16 t + j's windows are y[j .. j+W-1]
+    //   and z[j .. j+W-1], and every one of them contains position 15.  So T(16 t + j) = U[j] + (A + y[W] + ... + y[W+j-1])
+    //   + (B + z[W] + ... + z[W+j-1]) with U[j] = (y[j] + z[j]) + U[j+1] (from U[15] = y[15] + z[15] down), A = y[16] + ... + y[W-1],
+    //   B likewise (ascending, 0 at W = 16): fp32 additions of non-negative values only.  2 W + 46 LDS reads per thread and epoch.
+    //   W < 16: the two sums slide, L(k+1) = (L(k) + x[k-g]) - x[k-g-W], R(k+1) = (R(k) - x[k+g+1]) + x[k+g+W+1], from ascending-distance
+    //   sums at 16 t, in fp64 with the comparison: the residue of a strong bin is ~1e-16 of it (1e-7 of the floor at 90 dB).
+    // The 16 mask bits go to LDS as a half-word: lanes 2 w and 2 w + 1 form word w.  Then one lane per band counts its segments'
+    // detected bins (popcount per 32-bit word); the team below stores them and decides.
+    [[maybe_unused]] const lds_i32 *cfar_cnt = nullptr;
+    if constexpr ((C::OPT & kCfar) != 0) {
+      static_assert(!MAG && !C::SC16, "CFAR: energy mode, float samples");
+      lds_u16 *mk16 = reinterpret_cast<lds_u16 *>(rows + R3);        // [N / 16] half-words = [N / 32] words, behind the row totals
+      const lds_u32 *mk32 = reinterpret_cast<const lds_u32 *>(rows + R3);
+      lds_i32 *cnt = reinterpret_cast<lds_i32 *>(rows + R3 + N / 32);  // [n_bands]
+      const int g = p.cfar_guard, W = p.cfar_train;
+      const int k0 = 16 * t;
+      const int yl = k0 - g - W, zl = k0 + g + 1;   // first cell of the left / right run
+      unsigned bits = 0;
+      if (W >= 16) {   // uniform
+        const float sc = p.cfar_scale;
+        float u[16];
+        u[15] = spec[spec_phys((yl + 15) & (N - 1))] + spec[spec_phys((zl + 15) & (N - 1))];
+#pragma unroll
+        for (int q = 14; q >= 0; q--) u[q] = (spec[spec_phys((yl + q) & (N - 1))] + spec[spec_phys((zl + q) & (N - 1))]) + u[q + 1];
+        float a = 0.f, b = 0.f;
+        for (int q = 16; q < W; q++) {
+          a += spec[spec_phys((yl + q) & (N - 1))];
+          b += spec[spec_phys((zl + q) & (N - 1))];
+        }
+#pragma unroll
+        for (int j = 0; j < 16; j++) {
+          if (j > 0) {
+            a += spec[spec_phys((yl + W + j - 1) & (N - 1))];
+            b += spec[spec_phys((zl + W + j - 1) & (N - 1))];
+          }
+          const float x = spec[17 * t + j];  // spec_phys(16 t + j)
+          bits |= (x > sc * (u[j] + (a + b)) ? 1u : 0u) << j;
+        }
+      } else {
+        const double sd = (double)p.cfar_scale;
+        double lsum = 0.0, rsum = 0.0;
+        for (int i = g + 1; i <= g + W; i++) {
+          lsum += spec[spec_phys((k0 - i) & (N - 1))];
+          rsum += spec[spec_phys((k0 + i) & (N - 1))];
+        }
+#pragma unroll
+        for (int j = 0; j < 16; j++) {
+          const int k = k0 + j;
+          const float x = spec[17 * t + j];
+          bits |= ((double)x > sd * (lsum + rsum) ? 1u : 0u) << j;
+          if (j < 15) {
+            const float l_in = spec[spec_phys((k - g) & (N - 1))], l_out = spec[spec_phys((k - g - W) & (N - 1))];
+            const float r_out = spec[spec_phys((k + g + 1) & (N - 1))], r_in = spec[spec_phys((k + g + W + 1) & (N - 1))];
+            lsum = (lsum + (double)l_in) - (double)l_out;
+            rsum = (rsum - (double)r_out) + (double)r_in;
+          }
+        }
+      }
+      mk16[t] = (unsigned short)bits;
+      if constexpr (G::XWAVE) __syncthreads();
+      else wave_sync();
+      for (int b = t; b < p.n_bands; b += T) {
+        int n = 0;
+        for (int sg = tab[b], s1 = tab[b + 1]; sg < s1; sg++) {
+          const int hi = tab[256 + sg];
+          for (int k = tab[96 + sg]; k < hi;) {
+            const int w = k >> 5, e = hi < ((w + 1) << 5) ? hi : ((w + 1) << 5);
+            unsigned m = mk32[w] >> (k & 31);
+            if (e - k < 32) m &= (1u << (e - k)) - 1u;
+            n += __popc(m);
+            k = e;
+          }
+        }
+        cnt[b] = n;
+      }
+      if (active && p.cfar_mask != nullptr && t < N / 32) p.cfar_mask[epoch * (N / 32) + t] = mk32[t];
+      if constexpr (G::XWAVE) __syncthreads();
+      else wave_sync();
+      cfar_cnt = cnt;
+    }
+
     // LDS path: the first team of the group stores and decides.
     if (active && t < TEAM) {
       if (p.features != nullptr)
         for (int b = t; b < p.n_bands; b += TEAM) p.features[epoch * p.n_bands + b] = feat[b];
 
-      if (p.decide == CRN_DECIDE_ANN_K) {
+      if constexpr ((C::OPT & kCfar) != 0) {
+        // CFAR: occupied = at least min_bins detected bins; the decision counts the occupied bands, as the threshold rule does
+        int occ_bands = 0;
+        for (int b0 = 0; b0 < p.n_bands; b0 += TEAM) {
+          const int b = b0 + t;
+          const bool in = b < p.n_bands;
+          const int nb = in ? cfar_cnt[b] : 0;
+          const bool occ = in && nb >= p.cfar_min_bins;
+          if (in && p.occupancy != nullptr) p.occupancy[epoch * p.n_bands + b] = (uint8_t)occ;
+          if (in && p.cfar_band_bins != nullptr) p.cfar_band_bins[epoch * p.n_bands + b] = nb;
+          unsigned long long m = __ballot(occ);
+          if constexpr (TEAM == 32) m = (m >> (tid & 32)) & 0xffffffffull;
+          occ_bands += __popcll(m);
+        }
+        if (t == 0 && p.decision != nullptr) p.decision[epoch] = occ_bands;
+      } else if (p.decide == CRN_DECIDE_ANN_K) {
         ann_decide_team<TEAM>(p, w_ih, w_ho, epoch, true, lane, TEAM == 32 ? (tid & 32) : 0, feat[0], feat[1], feat[2], feat[3]);
       } else if (p.decide == CRN_DECIDE_THRESHOLD_K) {
         // lane i takes bands i, i + TEAM, ...; the count of occupied bands is a ballot, not a serial walk

@@ -130,6 +130,8 @@ enum : int {
                     // (instantiated by crn_kernels_sc16.hip: a library built with make SC16=1)
   kDeal = 1048576,  // sense_kernel_dealt (launches of a few epochs): one epoch per workgroup, its frames dealt to the lane groups; pass 3
                     // parks each frame's per-bin values in LDS (ph_pass3_park) and the accumulate is replayed in frame order afterwards
+  kCfar = 2097152,  // per-bin CA-CFAR on the LDS spectrum image after the band sums (crn_sense_set_cfar): bit mask, per-band counts and
+                    // the decision in place of the threshold rule (epoch_close, LDS form only)
 };
 
 template <int R3_, int NBUF_, bool PREFETCH_, bool NT_, bool MAG_, bool WIN_, bool TW2LDS_, int OCC_, bool FULL_, bool PK_, int OPT_ = 0>

@@ -489,9 +489,13 @@ static int ingest_create(crn_handle *h, int32_t n_streams, int32_t samples_per_p
   set_prewake(g);
   if (const char *e = std::getenv("CRN_INGEST_TRACE")) g->trace = std::atoi(e) != 0;
   if (const char *e = std::getenv("CRN_INGEST_WARM_GPU")) g->warm_gpu = std::atoi(e) != 0;
-  g->launcher = std::thread(launcher_main, g);
-  (void)crn_sense_ring_count(h, +1);
+  // attach (refused on a CFAR handle: the check and the claim are one step, under the handle's lock)
+  if (int rc = crn_sense_ring_count(h, +1)) {
+    crn_ingest_destroy(g);
+    return rc;
+  }
   g->attached = true;
+  g->launcher = std::thread(launcher_main, g);
   *out = g;
   return CRN_OK;
 }

@@ -58,6 +58,14 @@ struct SenseParams {
   int32_t *decision;
   uint8_t *occupancy;
   float *spectrum;
+  // CA-CFAR (crn_sense_set_cfar): read only by the kCfar kernels, which launch_sense picks when cfar_on != 0
+  int cfar_on;
+  int cfar_guard;          // g: guard cells on each side
+  int cfar_train;          // W: training cells on each side (1..64)
+  int cfar_min_bins;       // a band is occupied when at least this many of its bins are detected
+  float cfar_scale;        // alpha / (2 W): bin k is detected when sum_K P[k] > cfar_scale * (sum_K of its 2 W training cells)
+  uint32_t *cfar_mask;     // [n_epochs][N / 32] or null: bit k % 32 of word k / 32 = bin k detected
+  int32_t *cfar_band_bins; // [n_epochs][n_bands] or null: detected bins per band (segment listings counted as the band sums count them)
 };
 
 struct SynthParams {

@@ -46,9 +46,27 @@ bool sense_variant_traces(int v) { return measurement_variant_traces(v); }
 // Wire-format input: crn_kernels_sc16.hip, linked only into a library built with `make SC16=1` (a weak reference: null when absent).
 __attribute__((weak)) hipError_t launch_sense_sc16(const SenseParams &p, int fft_len, bool mag, bool win, int variant, hipStream_t stream, int *deal_rounds_run);
 
+// A handle with CFAR on (crn_sense_set_cfar; energy mode, float samples): the frame loop of the form the same handle runs with CFAR off
+// — so that the spectrum and the features are the same bits — closed through the LDS walk with the CFAR pass (crn_epoch_close.h).
+// No register-band, pruned-row, aligned-band or dealt forms.  The windowed forms below 4096 points take two workgroups per CU: at
+// three their frame loop spills (as the CFAR-off forms do), and a scratch reload in the loop waits behind the prefetch.
+template <int R3>
+static hipError_t launch_cfar(const SenseParams &p, bool win, hipStream_t stream) {
+  constexpr int kBase = kSpread | kLdsBlk | kPrioValu | kMulti | kCfar;
+  constexpr int kWinOcc = R3 == 16 ? 3 : 2;
+  if (win && p.hann_sym && p.L == Geo<R3>::N)
+    return launch_cfg<Cfg<R3, 1, true, true, false, true, true, kWinOcc, true, true, kBase | kHannSym | kTw2Early>>(p, stream);
+  if (win) return launch_cfg<Cfg<R3, 1, true, true, false, true, true, kWinOcc, false, true, kBase>>(p, stream);
+  if constexpr (R3 == 16) {
+    if (p.L == Geo<R3>::N) return launch_cfg<Cfg<R3, 1, true, true, false, false, true, 4, true, true, kBase | kTw1C>>(p, stream);
+  }
+  return launch_cfg<Cfg<R3, 1, true, true, false, false, false, 3, false, true, kBase>>(p, stream);
+}
+
 // The forms other than the default exist for N = 4096 only; other sizes always run the default.
 template <int R3>
 static hipError_t launch_r(const SenseParams &p, bool mag, bool win, int variant, hipStream_t stream, int *deal_rounds_run) {
+  if (p.cfar_on) return mag ? hipErrorInvalidValue : launch_cfar<R3>(p, win, stream);
   constexpr int kBase = kSpread | kLdsBlk | kPrioValu | kMulti;
   if constexpr (R3 <= 4) {   // a launch of a few epochs (crn_api.cpp sets deal_rounds): one epoch per workgroup, frames dealt to its lane groups
     if (p.deal_rounds > 0) {
