@@ -244,6 +244,40 @@ CRN_API int crn_sense_run_device_cfar(crn_handle *h, const float *d_iq, int64_t 
  * Windowed or overlapped frames correlate neighbouring bins and frames: the real false-alarm rate then differs from `pfa`. */
 CRN_API int crn_cfar_alpha(double pfa, int32_t frames_per_epoch, int32_t train, double *alpha);
 
+/* -- the CFAR detector family: greatest-of, smallest-of and ordered-statistic ------------------------------------------------
+ * The same P[k], guard and training cells, circular wrap, min_bins, band_bins, occupancy and decision as above; only the noise
+ * estimate Z[k] changes.  With L[k] and R[k] the means of the W training cells on each side:
+ *   CRN_CFAR_CA  Z = (L + R) / 2            (crn_sense_set_cfar)
+ *   CRN_CFAR_GO  Z = max(L, R)              holds the false-alarm rate where the floor steps (a band edge, filter roll-off)
+ *   CRN_CFAR_SO  Z = min(L, R)              resolves closely spaced carriers
+ *   CRN_CFAR_OS  Z = the rank-th smallest of the 2W cells, 1 <= rank <= 2W: ignores up to 2W - rank interferers in the window
+ * bin k detected  <=>  P[k] > alpha * Z[k].  OS is decided exactly by counting: at least `rank` training cells c with
+ * fl32(alpha c) < P[k] (both on the K-frame sums), which is P[k] > fl32(alpha X_(rank)), ties included. */
+typedef enum crn_cfar_method { CRN_CFAR_CA = 0, CRN_CFAR_GO = 1, CRN_CFAR_SO = 2, CRN_CFAR_OS = 3 } crn_cfar_method;
+
+/* crn_cfar_params plus the method and, for CRN_CFAR_OS only, the rank (0 for the other methods); reserved = 0. */
+typedef struct crn_cfar_params_ex {
+  int32_t method, guard, train, min_bins, rank, reserved;
+  float alpha;
+} crn_cfar_params_ex;
+
+/* crn_sense_set_cfar for every method: the same handle checks and parameter ranges, and CRN_ERR_ARG for a method outside 0..3, an OS
+ * rank outside 1..2 train, or a nonzero rank with another method.  NULL switches CFAR off.  A refused call leaves the detector as it
+ * was.  crn_sense_set_cfar(h, p) is this call with CRN_CFAR_CA and rank 0.  Ring and sc16 refusals apply to every method. */
+CRN_API int crn_sense_set_cfar_ex(crn_handle *h, const crn_cfar_params_ex *params);
+/* The detector in force, method and rank included, and whether CFAR is on.  Either pointer may be NULL.  (crn_sense_get_cfar fills
+ * the fields the two structs share, whichever method was set.) */
+CRN_API int crn_sense_get_cfar_ex(crn_handle *h, crn_cfar_params_ex *params, int32_t *on);
+/* alpha for a per-bin false-alarm probability `pfa` of `method`, host only, under crn_cfar_alpha's noise model (training cells and
+ * P are i.i.d. Gamma(K) in units of the noise power).  rank: 1..2 train for CRN_CFAR_OS, 0 otherwise.
+ *   CA  crn_cfar_alpha, exactly
+ *   GO  pfa = int Q(K, alpha s / W) 2 F(s) f(s) ds         f, F: the Gamma(WK) density and distribution (one side's sum)
+ *   SO  pfa = int Q(K, alpha s / W) 2 (1 - F(s)) f(s) ds
+ *   OS  pfa = int_0^1 Beta(u; rank, 2W - rank + 1) Q(K, alpha F_K^-1(u)) du
+ * Q(K, .) is the regularised upper incomplete gamma function.  Each is evaluated by quadrature and inverted by bisection in double.
+ * CRN_ERR_ARG for arguments out of range and for a pfa too small to reach. */
+CRN_API int crn_cfar_alpha_ex(int32_t method, double pfa, int32_t frames_per_epoch, int32_t train, int32_t rank, double *alpha);
+
 /* Allocate, now, the device scratch and pinned staging that crn_sense_run_host needs for up to
  * max_epochs dense epochs of full-length frames (and their per-bin spectra when want_spectrum != 0),
  * and load the kernels: a later crn_sense_run_host within that size allocates nothing.  An engine

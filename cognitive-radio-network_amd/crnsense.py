@@ -45,6 +45,7 @@ EXPORTS = [
     "crn_sense_reserve_host", "crn_sense_set_timing", "crn_sense_get_stats", "crn_ingest_get_stats",
     "crn_monitor_rows_device",
     "crn_sense_set_cfar", "crn_sense_get_cfar", "crn_sense_run_device_cfar", "crn_cfar_alpha",
+    "crn_sense_set_cfar_ex", "crn_sense_get_cfar_ex", "crn_cfar_alpha_ex",
     "crn_comm_unique_id", "crn_comm_create", "crn_comm_local", "crn_comm_allgather", "crn_comm_gathered",
     "crn_comm_finish", "crn_comm_destroy", "crn_comm_local_addr", "crn_comm_wait", "crn_comm_info",
     "crn_last_error", "crn_abi_version", "crn_build_info",
@@ -78,6 +79,16 @@ class Out(C.Structure):
 class CfarParams(C.Structure):
     """crn_cfar_params: per-bin CA-CFAR (crn_sense_set_cfar)."""
     _fields_ = [("guard", C.c_int32), ("train", C.c_int32), ("min_bins", C.c_int32), ("reserved", C.c_int32), ("alpha", C.c_float)]
+
+
+class CfarParamsEx(C.Structure):
+    """crn_cfar_params_ex: per-bin CFAR of any method (crn_sense_set_cfar_ex)."""
+    _fields_ = [("method", C.c_int32), ("guard", C.c_int32), ("train", C.c_int32), ("min_bins", C.c_int32), ("rank", C.c_int32),
+                ("reserved", C.c_int32), ("alpha", C.c_float)]
+
+
+CFAR_CA, CFAR_GO, CFAR_SO, CFAR_OS = 0, 1, 2, 3    # crn_cfar_method
+CFAR_METHODS = {"ca": CFAR_CA, "go": CFAR_GO, "so": CFAR_SO, "os": CFAR_OS}
 
 
 class EpochResult(C.Structure):
@@ -188,6 +199,9 @@ def lib():
         L.crn_sense_run_device_cfar.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.POINTER(Out),
                                                 C.c_void_p, C.c_void_p, C.c_void_p]
         L.crn_cfar_alpha.argtypes = [C.c_double, C.c_int32, C.c_int32, C.POINTER(C.c_double)]
+        L.crn_sense_set_cfar_ex.argtypes = [C.c_void_p, C.POINTER(CfarParamsEx)]
+        L.crn_sense_get_cfar_ex.argtypes = [C.c_void_p, C.POINTER(CfarParamsEx), C.POINTER(C.c_int32)]
+        L.crn_cfar_alpha_ex.argtypes = [C.c_int32, C.c_double, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_double)]
         L.crn_ingest_create.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]
         L.crn_ingest_push.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
         L.crn_ingest_flush.argtypes = [C.c_void_p]
@@ -276,11 +290,29 @@ def cfg_welch_scaled(fft_len, frames_per_epoch=8, lam=4.0):
     return c
 
 
-def cfar_alpha(pfa, K, train):
+def _cfar_method(method):
+    if method not in CFAR_METHODS:
+        raise ValueError(f"CFAR method must be one of {sorted(CFAR_METHODS)}, not {method!r}")
+    return CFAR_METHODS[method]
+
+
+def cfar_os_rank(train):
+    """The default OS-CFAR rank: 3/4 of the 2 W training cells."""
+    return 3 * 2 * int(train) // 4
+
+
+def cfar_alpha(pfa, K, train, method="ca", rank=None):
     """CFAR scale alpha for a per-bin false-alarm probability pfa at K frames per epoch and `train` training cells per side
-    (white complex Gaussian noise, rectangular window, disjoint frames: include/crn_sense.h, crn_cfar_alpha)."""
+    (white complex Gaussian noise, rectangular window, disjoint frames: include/crn_sense.h, crn_cfar_alpha / crn_cfar_alpha_ex).
+    method: "ca", "go", "so" or "os"; rank (OS only) defaults to cfar_os_rank(train)."""
     a = C.c_double()
-    check(lib().crn_cfar_alpha(float(pfa), int(K), int(train), C.byref(a)), "crn_cfar_alpha")
+    if method == "ca" and rank is None:
+        check(lib().crn_cfar_alpha(float(pfa), int(K), int(train), C.byref(a)), "crn_cfar_alpha")
+        return a.value
+    m = _cfar_method(method)
+    if rank is None:
+        rank = cfar_os_rank(train) if m == CFAR_OS else 0
+    check(lib().crn_cfar_alpha_ex(m, float(pfa), int(K), int(train), int(rank), C.byref(a)), "crn_cfar_alpha_ex")
     return a.value
 
 
@@ -430,21 +462,36 @@ class Sensor:
         check(fn(self._h, iq_ptr, n_epochs, L, epoch_stride, C.byref(o), C.c_void_p(stream or None)),
               "crn_sense_run_device_sc16" if sc16 else "crn_sense_run_device")
 
-    def set_cfar(self, guard, train=16, alpha=None, min_bins=1):
-        """Per-bin CA-CFAR on (guard, train, alpha, min_bins), or off with set_cfar(None).  alpha defaults to cfar_alpha(1e-3, K, train)."""
+    def set_cfar(self, guard, train=16, alpha=None, min_bins=1, *, method="ca", rank=None):
+        """Per-bin CFAR on (guard, train, alpha, min_bins), or off with set_cfar(None).  method: "ca" (cell averaging), "go" (greatest
+        of), "so" (smallest of) or "os" (ordered statistic, the rank-th smallest of the 2 W cells; rank defaults to cfar_os_rank(train)).
+        alpha defaults to cfar_alpha(1e-3, K, train, method, rank)."""
         if guard is None:
             check(lib().crn_sense_set_cfar(self._h, None), "crn_sense_set_cfar")
             return
+        m = _cfar_method(method)
+        if rank is None:
+            rank = cfar_os_rank(train) if m == CFAR_OS else 0
         if alpha is None:
-            alpha = cfar_alpha(1e-3, self.cfg.frames_per_epoch, train)
-        q = CfarParams(guard=int(guard), train=int(train), min_bins=int(min_bins), reserved=0, alpha=float(alpha))
-        check(lib().crn_sense_set_cfar(self._h, C.byref(q)), "crn_sense_set_cfar")
+            alpha = cfar_alpha(1e-3, self.cfg.frames_per_epoch, train, method, rank)
+        if m == CFAR_CA and rank == 0:
+            q = CfarParams(guard=int(guard), train=int(train), min_bins=int(min_bins), reserved=0, alpha=float(alpha))
+            check(lib().crn_sense_set_cfar(self._h, C.byref(q)), "crn_sense_set_cfar")
+            return
+        q = CfarParamsEx(method=m, guard=int(guard), train=int(train), min_bins=int(min_bins), rank=int(rank), reserved=0,
+                         alpha=float(alpha))
+        check(lib().crn_sense_set_cfar_ex(self._h, C.byref(q)), "crn_sense_set_cfar_ex")
 
     def get_cfar(self):
-        """None while CFAR is off, else {"guard", "train", "alpha", "min_bins"}."""
-        q, on = CfarParams(), C.c_int32()
-        check(lib().crn_sense_get_cfar(self._h, C.byref(q), C.byref(on)), "crn_sense_get_cfar")
-        return {"guard": q.guard, "train": q.train, "alpha": q.alpha, "min_bins": q.min_bins} if on.value else None
+        """None while CFAR is off, else {"guard", "train", "alpha", "min_bins"}, plus "method" and "rank" for a method other than CA."""
+        q, on = CfarParamsEx(), C.c_int32()
+        check(lib().crn_sense_get_cfar_ex(self._h, C.byref(q), C.byref(on)), "crn_sense_get_cfar_ex")
+        if not on.value:
+            return None
+        d = {"guard": q.guard, "train": q.train, "alpha": q.alpha, "min_bins": q.min_bins}
+        if q.method != CFAR_CA:
+            d.update(method={v: k for k, v in CFAR_METHODS.items()}[q.method], rank=q.rank)
+        return d
 
     def run_device_cfar(self, iq_ptr, n_epochs, L, out_ptrs, mask_ptr=0, band_bins_ptr=0, stream=0, epoch_stride=0):
         """run_device plus the CFAR outputs: mask_ptr [n_epochs][fft_len / 32] uint32, band_bins_ptr [n_epochs][n_bands] int32 (device

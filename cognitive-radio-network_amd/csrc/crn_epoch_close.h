@@ -444,17 +444,26 @@ CRN_DEV void epoch_close(FrameCtx<C> &c, const SenseParams &p, long long epoch_b
 
     feat = featl;
 
-    // CA-CFAR (kCfar): bin k is detected when P[k] > alpha Z[k], Z[k] the mean of the 2 W training cells g < |i| <= g + W around it,
-    // circular over the N bins.  Both sides carry the same 1 / K, so the test runs on the K-frame sums in the image:
-    // x[k] > s T(k), T(k) the sum of the 2 W training cells, s = alpha / 2 W rounded once to fp32 on the host.  Thread t owns bins
-    // 16 t .. 16 t + 15 (the band sums' blocks).  A window sum must never be formed by subtracting a cell that left it: a strong bin
-    // that enters and leaves a sliding fp32 sum leaves ~ulp32(strong bin) behind, 30-50 % of the training sum at 80-90 dB over the floor.
-    //   W >= 16: with y[i] = x[16 t - g - W + i] (left) and z[i] = x[16 t + g + 1 + i] (right), bin 16 t + j's windows are y[j .. j+W-1]
-    //   and z[j .. j+W-1], and every one of them contains position 15.  So T(16 t + j) = U[j] + (A + y[W] + ... + y[W+j-1])
-    //   + (B + z[W] + ... + z[W+j-1]) with U[j] = (y[j] + z[j]) + U[j+1] (from U[15] = y[15] + z[15] down), A = y[16] + ... + y[W-1],
-    //   B likewise (ascending, 0 at W = 16): fp32 additions of non-negative values only.  2 W + 46 LDS reads per thread and epoch.
+    // CFAR (kCfar): bin k is detected when P[k] > alpha Z[k], Z[k] the method's noise estimate from the 2 W training cells
+    // g < |i| <= g + W around it, circular over the N bins (include/crn_sense.h, crn_cfar_method).  Every cell carries the same 1 / K,
+    // so the test runs on the K-frame sums in the image with s = cfar_scale, rounded once to fp32 on the host: CA x[k] > s (T_L + T_R)
+    // with s = alpha / 2 W, GO / SO x[k] > s max / min(T_L, T_R) with s = alpha / W, T_L and T_R the two sides' sums.  Thread t owns
+    // bins 16 t .. 16 t + 15 (the band sums' blocks).  With y[i] = x[16 t - g - W + i] (left) and z[i] = x[16 t + g + 1 + i] (right),
+    // bin 16 t + j's windows are y[j .. j+W-1] and z[j .. j+W-1].  The method is a launch parameter: one kernel holds all four.
+    //   A window sum must never be formed by subtracting a cell that left it: a strong bin that enters and leaves a sliding fp32 sum
+    //   leaves ~ulp32(strong bin) behind, 30-50 % of the training sum at 80-90 dB over the floor.
+    //   W >= 16: every window contains position 15.  CA: T(16 t + j) = U[j] + (A + y[W] + ... + y[W+j-1]) + (B + z[W] + ... + z[W+j-1])
+    //   with U[j] = (y[j] + z[j]) + U[j+1] (from U[15] = y[15] + z[15] down), A = y[16] + ... + y[W-1], B likewise (ascending, 0 at
+    //   W = 16): fp32 additions of non-negative values only.  2 W + 46 LDS reads per thread and epoch.  GO / SO keep the sides apart:
+    //   T_L(16 t + j) = U_L[j] + (A + y[W] + ... + y[W+j-1]) with U_L[j] = y[j] + U_L[j+1], T_R likewise.
     //   W < 16: the two sums slide, L(k+1) = (L(k) + x[k-g]) - x[k-g-W], R(k+1) = (R(k) - x[k+g+1]) + x[k+g+W+1], from ascending-distance
     //   sums at 16 t, in fp64 with the comparison: the residue of a strong bin is ~1e-16 of it (1e-7 of the floor at 90 dB).
+    //   OS (s = alpha): bin k is detected when at least `rank` of its 2 W cells c have fl32(s c) < x[k], which is x[k] > fl32(alpha
+    //   X_(rank)) because rounding is monotone: a count, no sort.  Cell-major, so that no register array is indexed at run time, in
+    //   passes of B = 4 bins: each side's W + B - 1 cells of a pass are read once, scaled once and compared with the pass's bins that see
+    //   them.  Cell q (0 <= q < W + B - 1, counted from the pass's first bin) is in bin j's windows for j <= q < j + W.  At W >= B the
+    //   head cells q < B - 1 and the tail cells q >= W are unrolled (their bin ranges are compile-time) and the cells B - 1 <= q < W in
+    //   between are seen by all B bins; below B each cell tests its range.
     // The 16 mask bits go to LDS as a half-word: lanes 2 w and 2 w + 1 form word w.  Then one lane per band counts its segments'
     // detected bins (popcount per 32-bit word); the team below stores them and decides.
     [[maybe_unused]] const lds_i32 *cfar_cnt = nullptr;
@@ -466,46 +475,144 @@ CRN_DEV void epoch_close(FrameCtx<C> &c, const SenseParams &p, long long epoch_b
       const int g = p.cfar_guard, W = p.cfar_train;
       const int k0 = 16 * t;
       const int yl = k0 - g - W, zl = k0 + g + 1;   // first cell of the left / right run
+      const int method = p.cfar_method;
       unsigned bits = 0;
-      if (W >= 16) {   // uniform
+      if (method == CRN_CFAR_OS_K) {
         const float sc = p.cfar_scale;
-        float u[16];
-        u[15] = spec[spec_phys((yl + 15) & (N - 1))] + spec[spec_phys((zl + 15) & (N - 1))];
+        const int rank = p.cfar_rank;
+        constexpr int B = 4;   // bins per pass: B counts and B bins beside the prefetched frame (8 of each spilled)
 #pragma unroll
-        for (int q = 14; q >= 0; q--) u[q] = (spec[spec_phys((yl + q) & (N - 1))] + spec[spec_phys((zl + q) & (N - 1))]) + u[q + 1];
-        float a = 0.f, b = 0.f;
-        for (int q = 16; q < W; q++) {
-          a += spec[spec_phys((yl + q) & (N - 1))];
-          b += spec[spec_phys((zl + q) & (N - 1))];
-        }
+        for (int j0 = 0; j0 < 16; j0 += B) {
+          float x[B];
+          int n[B];
 #pragma unroll
-        for (int j = 0; j < 16; j++) {
-          if (j > 0) {
-            a += spec[spec_phys((yl + W + j - 1) & (N - 1))];
-            b += spec[spec_phys((zl + W + j - 1) & (N - 1))];
+          for (int j = 0; j < B; j++) {
+            x[j] = spec[17 * t + j0 + j];  // spec_phys(16 t + j0 + j)
+            n[j] = 0;
           }
-          const float x = spec[17 * t + j];  // spec_phys(16 t + j)
-          bits |= (x > sc * (u[j] + (a + b)) ? 1u : 0u) << j;
-        }
-      } else {
-        const double sd = (double)p.cfar_scale;
-        double lsum = 0.0, rsum = 0.0;
-        for (int i = g + 1; i <= g + W; i++) {
-          lsum += spec[spec_phys((k0 - i) & (N - 1))];
-          rsum += spec[spec_phys((k0 + i) & (N - 1))];
-        }
+          // cell j0 + q of both runs against the pass's bins jlo .. jhi (bin j0 + j sees cells j0 + j .. j0 + j + W - 1)
+          auto count = [&](int q, int jlo, int jhi) {
+            const float cl = sc * spec[spec_phys((yl + j0 + q) & (N - 1))], cr = sc * spec[spec_phys((zl + j0 + q) & (N - 1))];
 #pragma unroll
-        for (int j = 0; j < 16; j++) {
-          const int k = k0 + j;
-          const float x = spec[17 * t + j];
-          bits |= ((double)x > sd * (lsum + rsum) ? 1u : 0u) << j;
-          if (j < 15) {
-            const float l_in = spec[spec_phys((k - g) & (N - 1))], l_out = spec[spec_phys((k - g - W) & (N - 1))];
-            const float r_out = spec[spec_phys((k + g + 1) & (N - 1))], r_in = spec[spec_phys((k + g + W + 1) & (N - 1))];
-            lsum = (lsum + (double)l_in) - (double)l_out;
-            rsum = (rsum - (double)r_out) + (double)r_in;
+            for (int j = 0; j < B; j++)
+              if (j >= jlo && j <= jhi) n[j] += (cl < x[j] ? 1 : 0) + (cr < x[j] ? 1 : 0);
+          };
+          if (W >= B) {
+#pragma unroll
+            for (int q = 0; q < B - 1; q++) count(q, 0, q);
+            for (int q = B - 1; q < W; q++) count(q, 0, B - 1);
+#pragma unroll
+            for (int r = 0; r < B - 1; r++) count(W + r, r + 1, B - 1);
+          } else {
+            for (int q = 0; q < W + B - 1; q++) {
+              const float cl = sc * spec[spec_phys((yl + j0 + q) & (N - 1))], cr = sc * spec[spec_phys((zl + j0 + q) & (N - 1))];
+#pragma unroll
+              for (int j = 0; j < B; j++)
+                n[j] += (unsigned)(q - j) < (unsigned)W ? (cl < x[j] ? 1 : 0) + (cr < x[j] ? 1 : 0) : 0;
+            }
+          }
+#pragma unroll
+          for (int j = 0; j < B; j++) bits |= (n[j] >= rank ? 1u : 0u) << (j0 + j);
+        }
+      } else if (method == CRN_CFAR_CA_K) {
+        if (W >= 16) {   // uniform
+          const float sc = p.cfar_scale;
+          float u[16];
+          u[15] = spec[spec_phys((yl + 15) & (N - 1))] + spec[spec_phys((zl + 15) & (N - 1))];
+#pragma unroll
+          for (int q = 14; q >= 0; q--) u[q] = (spec[spec_phys((yl + q) & (N - 1))] + spec[spec_phys((zl + q) & (N - 1))]) + u[q + 1];
+          float a = 0.f, b = 0.f;
+          for (int q = 16; q < W; q++) {
+            a += spec[spec_phys((yl + q) & (N - 1))];
+            b += spec[spec_phys((zl + q) & (N - 1))];
+          }
+#pragma unroll
+          for (int j = 0; j < 16; j++) {
+            if (j > 0) {
+              a += spec[spec_phys((yl + W + j - 1) & (N - 1))];
+              b += spec[spec_phys((zl + W + j - 1) & (N - 1))];
+            }
+            const float x = spec[17 * t + j];  // spec_phys(16 t + j)
+            bits |= (x > sc * (u[j] + (a + b)) ? 1u : 0u) << j;
+          }
+        } else {
+          const double sd = (double)p.cfar_scale;
+          double lsum = 0.0, rsum = 0.0;
+          for (int i = g + 1; i <= g + W; i++) {
+            lsum += spec[spec_phys((k0 - i) & (N - 1))];
+            rsum += spec[spec_phys((k0 + i) & (N - 1))];
+          }
+#pragma unroll
+          for (int j = 0; j < 16; j++) {
+            const int k = k0 + j;
+            const float x = spec[17 * t + j];
+            bits |= ((double)x > sd * (lsum + rsum) ? 1u : 0u) << j;
+            if (j < 15) {
+              const float l_in = spec[spec_phys((k - g) & (N - 1))], l_out = spec[spec_phys((k - g - W) & (N - 1))];
+              const float r_out = spec[spec_phys((k + g + 1) & (N - 1))], r_in = spec[spec_phys((k + g + W + 1) & (N - 1))];
+              lsum = (lsum + (double)l_in) - (double)l_out;
+              rsum = (rsum - (double)r_out) + (double)r_in;
+            }
           }
         }
+      } else {   // GO / SO: the same passes with max or min, each its own loop (no select, no sign constant held through the frame loop)
+        auto go_so = [&](auto pick) {
+          if (W >= 16) {   // uniform, in two halves of 8 bins (two suffix arrays of 16 spill); a and b carry over, so every sum is as above
+            const float sc = p.cfar_scale;
+            float a = 0.f, b = 0.f;
+            for (int q = 16; q < W; q++) {
+              a += spec[spec_phys((yl + q) & (N - 1))];
+              b += spec[spec_phys((zl + q) & (N - 1))];
+            }
+#pragma unroll
+            for (int j0 = 0; j0 < 16; j0 += 8) {
+              float ul[8], ur[8];
+              float sl = spec[spec_phys((yl + 15) & (N - 1))], sr = spec[spec_phys((zl + 15) & (N - 1))];
+#pragma unroll
+              for (int q = 15; q >= j0; q--) {
+                if (q < 15) {
+                  sl = spec[spec_phys((yl + q) & (N - 1))] + sl;
+                  sr = spec[spec_phys((zl + q) & (N - 1))] + sr;
+                }
+                if (q < j0 + 8) {
+                  ul[q - j0] = sl;
+                  ur[q - j0] = sr;
+                }
+              }
+#pragma unroll
+              for (int j = j0; j < j0 + 8; j++) {
+                if (j > 0) {
+                  a += spec[spec_phys((yl + W + j - 1) & (N - 1))];
+                  b += spec[spec_phys((zl + W + j - 1) & (N - 1))];
+                }
+                const float tl = ul[j - j0] + a, tr = ur[j - j0] + b;
+                const float x = spec[17 * t + j];  // spec_phys(16 t + j)
+                bits |= (x > sc * pick(tl, tr) ? 1u : 0u) << j;
+              }
+            }
+          } else {
+            const double sd = (double)p.cfar_scale;
+            double lsum = 0.0, rsum = 0.0;
+            for (int i = g + 1; i <= g + W; i++) {
+              lsum += spec[spec_phys((k0 - i) & (N - 1))];
+              rsum += spec[spec_phys((k0 + i) & (N - 1))];
+            }
+#pragma unroll
+            for (int j = 0; j < 16; j++) {
+              const int k = k0 + j;
+              const float x = spec[17 * t + j];
+              bits |= ((double)x > sd * pick(lsum, rsum) ? 1u : 0u) << j;
+              if (j < 15) {
+                const float l_in = spec[spec_phys((k - g) & (N - 1))], l_out = spec[spec_phys((k - g - W) & (N - 1))];
+                const float r_out = spec[spec_phys((k + g + 1) & (N - 1))], r_in = spec[spec_phys((k + g + W + 1) & (N - 1))];
+                lsum = (lsum + (double)l_in) - (double)l_out;
+                rsum = (rsum - (double)r_out) + (double)r_in;
+              }
+            }
+          }
+        };
+        if (method == CRN_CFAR_GO_K) go_so([](auto u, auto v) { return u > v ? u : v; });
+        else go_so([](auto u, auto v) { return u < v ? u : v; });
       }
       mk16[t] = (unsigned short)bits;
       if constexpr (G::XWAVE) __syncthreads();

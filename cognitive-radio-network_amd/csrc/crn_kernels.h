@@ -11,6 +11,7 @@ constexpr int kBandTabWords = 656;   // SenseParams::band_tab, copied to LDS by 
 constexpr int kRowEntryWords = 32;   // row-entry slots of the register-resident band sums: 32 / R3 per row
 
 enum { CRN_DECIDE_ANN_K = 0, CRN_DECIDE_THRESHOLD_K = 1, CRN_DECIDE_NONE_K = 2 };  // == crn_decide
+enum { CRN_CFAR_CA_K = 0, CRN_CFAR_GO_K = 1, CRN_CFAR_SO_K = 2, CRN_CFAR_OS_K = 3 };     // == crn_cfar_method
 
 struct SenseParams {
   // input stream
@@ -63,9 +64,12 @@ struct SenseParams {
   int cfar_guard;          // g: guard cells on each side
   int cfar_train;          // W: training cells on each side (1..64)
   int cfar_min_bins;       // a band is occupied when at least this many of its bins are detected
-  float cfar_scale;        // alpha / (2 W): bin k is detected when sum_K P[k] > cfar_scale * (sum_K of its 2 W training cells)
+  float cfar_scale;        // bin k is detected when sum_K P[k] > cfar_scale * (the method's statistic of the K-frame training sums):
+                           // CA alpha / (2 W) on both sides' total, GO / SO alpha / W on the larger / smaller side, OS alpha on each cell
   uint32_t *cfar_mask;     // [n_epochs][N / 32] or null: bit k % 32 of word k / 32 = bin k detected
   int32_t *cfar_band_bins; // [n_epochs][n_bands] or null: detected bins per band (segment listings counted as the band sums count them)
+  int cfar_method;         // crn_cfar_method (crn_sense_set_cfar_ex)
+  int cfar_rank;           // OS: detected when at least this many training cells c have fl32(cfar_scale c) < sum_K P[k]
 };
 
 struct SynthParams {
