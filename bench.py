@@ -23,15 +23,20 @@ Warm-up: W untimed steps, topped up to ~50 ms of launches when W is small (clock
 exactly K timed steps between barrier + synchronize pairs, every launch bracketed by its own event
 pair on the launch stream.
 
+A plain run does only what the headline needs: it sets up, warms up, times the K steps, writes --dump-outputs and prints
+the line.  --full also checks the timed outputs (against the driven pattern, the oracle and, at N > 1, the gathered vector)
+and measures config.alt, cpu_baseline and the rocprofv3 counter passes behind roofline.traffic / roofline_valu.issue_frac;
+a plain line carries the committed figures for those two and null for the others.
+
 Prints ONE JSON line on rank 0 (contract in the task statement), including
   roofline      HBM-bound: algorithmic bytes (8 B per unique input sample) / mean kernel time from the
                 per-launch events, against the 8 TB/s peak; min / median / max per launch alongside
   roofline_valu (windowed / Welch modes, which are VALU-issue-bound) algorithmic flops against the fp32
                 vector peak, plus the measured VALU-busy fraction at the measured clock from the committed
                 counter passes of the same command (profiles/valu_counters.json)
-  config.alt    (N = 1, headline workload) the same kernel on SURVEY.md §8(d)'s 2 GiB batch, and the
+  config.alt    (--full, N = 1, headline workload) the same kernel on SURVEY.md §8(d)'s 2 GiB batch, and the
                 kernel any other band table / a spectrum request gets (no row pruning)
-  cpu_baseline  the oracle (CPU restatement of the reference path, built -O2 -march=native on this box)
+  cpu_baseline  (--full) the oracle (CPU restatement of the reference path, built -O2 -march=native on this box)
                 timed on this box's host cores on a bounded sample of the same data: the threads the process may run at once (`value`)
                 and one thread — the reference's own topology — BASELINE.md §3's protocol: 2 warm-up passes, median of 10.  At N > 1
                 rank 0 measures it after the timed region while the other ranks wait, so every 1 / 2 / 4 / 8-GPU line carries it.
@@ -224,9 +229,8 @@ def live_counters(args, epochs, passes):
     tmp = tempfile.mkdtemp(prefix="crn_pmc_", dir="/tmp")
     # the interpreter running this file, resolved to the real binary: no shim or wrapper script may sit between rocprofv3's `--`
     # and the program (the profiler's preloaded library initialises the GPU, and an exec after that is refused on this pool)
-    child = [os.path.realpath(sys.executable), os.path.abspath(__file__), "--steps", "5", "--warmup", "20", "--cpu-epochs", "0", "--no-alt",
-             "--no-live-traffic", "--fft", str(args.fft), "--mode", args.mode, "--variant", str(args.variant),
-             "--epochs", str(epochs)]
+    child = [os.path.realpath(sys.executable), os.path.abspath(__file__), "--steps", "5", "--warmup", "20",   # a plain run: launches only
+             "--fft", str(args.fft), "--mode", args.mode, "--variant", str(args.variant), "--epochs", str(epochs)]
     if args.frames > 0:
         child += ["--frames", str(args.frames)]
     if getattr(args, "wire_format", False):
@@ -317,6 +321,10 @@ def main():
                     help="scan = cfg4's wideband scan: the welch kernel, streams of 64 channels sharded over the ranks")
     ap.add_argument("--variant", type=int, default=0, help="kernel variant (0 = default)")
     ap.add_argument("--frames", type=int, default=0, help="frames per epoch K (0 = the configuration's own, 10)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also check the outputs and measure what the headline does not need: config.alt, "
+                         "cpu_baseline and the rocprofv3 counter passes (--cpu-epochs, --no-alt, --no-check and --no-live-traffic "
+                         "act only with --full)")
     ap.add_argument("--cpu-epochs", type=int, default=-1, help="oracle sample size (-1 = auto, 0 = skip the CPU baseline)")
     ap.add_argument("--no-alt", action="store_true", help="skip the config.alt legs (2 GiB batch, unpruned kernel)")
     ap.add_argument("--span-events", action="store_true",
@@ -351,6 +359,8 @@ def main():
     args = ap.parse_args()
     if args.steps < 1:
         ap.error("--steps must be at least 1")
+    if not args.full:
+        args.no_check, args.cpu_epochs, args.no_alt, args.no_live_traffic = True, 0, True, True
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` without a launcher: start the N rank processes ourselves.  This process has made no GPU

@@ -1,5 +1,6 @@
-"""bench.py's contract (one JSON line on stdout with roofline and cpu_baseline), and the N > 1 code path
-dry-run on one GPU: RCCL group of one rank, occupancy all-gather overlapped with the next launch."""
+"""bench.py's contract (one JSON line on stdout with roofline, and cpu_baseline with --full), and the N > 1 code path
+dry-run on one GPU: RCCL group of one rank, occupancy all-gather overlapped with the next launch.  A test that needs the output
+checks or a figure a plain run leaves out passes --full."""
 import json
 import os
 import subprocess
@@ -27,7 +28,7 @@ def _run(*extra, epochs=("--epochs", "512")):
 
 
 def test_bench_prints_one_json_line_with_roofline_and_cpu_baseline(built):
-    d = _run("--cpu-epochs", "64")
+    d = _run("--full", "--cpu-epochs", "64")
     for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
                 "vs_baseline", "dtype", "data", "config", "roofline", "cpu_baseline"):
         assert key in d
@@ -63,11 +64,23 @@ def test_bench_dump_outputs_are_the_same_on_every_run(built, tmp_path):
     assert occ.shape == (512, 4) and occ.any() and not occ.all()
 
 
+def test_bench_plain_run_leaves_everything_else_to_full(built):
+    """Without --full the line is the headline and what its timed steps give: on the default batch, and without any of the options
+    that turn them off, no config.alt leg, no CPU baseline and no counter pass runs (roofline.traffic is the committed figure)."""
+    d = _run("--live", epochs=())     # ("--live": no --no-live-traffic)
+    assert d["steps"] == 4 and d["warmup"] == 2 and d["unit"] == "Msamples/s" and d["higher_is_better"] is True and d["dtype"] == "f32"
+    assert d["metric"].startswith("Msamples/s IQ through FFT+energy-detect, 4096-pt x 3ch")
+    assert abs(d["value"] * d["ms_per_step"] * 1e-3 * 1e6 / (28672 * 40960) - 1) < 1e-9     # Msamples/s of the timed steps
+    assert d["roofline"]["kernel_ms_mean"] <= d["ms_per_step"]
+    assert d["cpu_baseline"] is None and d["config"]["alt"] is None and d["config"]["cfgH_as_worded_frac"] is None
+    assert d["roofline"]["traffic_source"].startswith("committed"), d["roofline"]["traffic_source"]
+
+
 def test_bench_default_batch_with_every_alt_leg_and_the_cpu_check(built):
     """The driver's shape: the default 8.75 GiB batch, so that the config.alt legs run (SURVEY §8(d)'s 2 GiB batch on one and on two
     streams, the unpruned kernel) — and the CPU sample check after them still reads the headline launch's results, not a leg's.
     Nothing outside north_star rides in the default line: no 16-bit-input or wire-format legs (--wire-format is opt-in)."""
-    d = _run("--cpu-epochs", "64", epochs=())
+    d = _run("--full", "--cpu-epochs", "64", epochs=())
     alt = d["config"]["alt"]
     assert set(alt) == {"cfgH_2GiB_batch", "cfgH_2GiB_batch_two_streams", "unpruned"}
     two = alt.pop("cfgH_2GiB_batch_two_streams")
@@ -93,7 +106,7 @@ def test_bench_measures_hbm_traffic_in_the_run(built):
     import shutil
     if shutil.which("rocprofv3") is None:
         pytest.skip("rocprofv3 not on PATH")
-    d = _run("--cpu-epochs", "0", "--live")
+    d = _run("--full", "--cpu-epochs", "0", "--live")
     r = d["roofline"]
     assert r["traffic_source"].startswith("measured in this run"), r["traffic_source"]
     assert abs(r["traffic"] / d["config"]["bytes_per_gpu_per_step"] - 1) < 0.01, r
@@ -101,7 +114,7 @@ def test_bench_measures_hbm_traffic_in_the_run(built):
 
 @pytest.mark.parametrize("mode", [[], ["--mode", "ref"], ["--mode", "welch"], ["--mode", "scan"]])
 def test_bench_collective_path_on_one_gpu(built, mode):
-    d = _run("--cpu-epochs", "0", "--force-collective", *mode)
+    d = _run("--full", "--cpu-epochs", "0", "--force-collective", *mode)
     assert "RCCL all-gather of occupancy" in d["config"]["parallelism"]
     assert d["value"] > 0 and d["cpu_baseline"] is None
     # one real RCCL rank: the line says what RCCL itself reports for the communicator the gathers ran on
@@ -117,11 +130,11 @@ def test_bench_two_streams_per_gpu(built):
     """--two-streams (what --scaling strong selects by itself for shares under 4 GiB): launches alternate between two streams with an
     output set each and four exchange slots; the roofline is priced from the span over both streams; the last launch's outputs still
     pass the oracle check and the gathered-vector check."""
-    d = _run("--cpu-epochs", "0", "--two-streams", "--force-collective")
+    d = _run("--full", "--cpu-epochs", "0", "--two-streams", "--force-collective")
     assert d["config"]["streams_per_gpu"] == 2 and "two streams" in d["roofline"]["events"]
     assert d["config"]["rccl"]["nranks"] == 1 and d["config"]["rccl"]["gathers_per_rank"][0] >= d["steps"]
     assert 0 < d["roofline"]["frac"] < 1 and d["roofline"]["kernel_ms_min"] == d["roofline"]["kernel_ms_max"]   # one span figure
-    d = _run("--cpu-epochs", "0", "--two-streams", "--mode", "welch")
+    d = _run("--full", "--cpu-epochs", "0", "--two-streams", "--mode", "welch")
     assert d["config"]["streams_per_gpu"] == 2 and d["value"] > 0
 
 
@@ -150,13 +163,13 @@ def test_bench_wire_format_mode(built):
     (bench.py loads the optional libcrnsense_sc16.so for it.)"""
     if not os.path.exists(os.path.join(ROOT, "cognitive-radio-network_amd", "libcrnsense_sc16.so")):
         pytest.skip("libcrnsense_sc16.so was not built (make -C csrc SC16=1)")
-    d = _run("--cpu-epochs", "0", "--wire-format")
+    d = _run("--full", "--cpu-epochs", "0", "--wire-format")
     assert d["config"]["bytes_per_gpu_per_step"] == 512 * 40960 * 4
     assert "NOT THE HEADLINE CONFIGURATION" in d["config"]["workload"] and d["roofline"]["traffic"] is None   # (--no-live-traffic here)
-    d = _run("--cpu-epochs", "0", "--wire-format", "--live")                  # measured in the run: 4 B per sample, read once
+    d = _run("--full", "--cpu-epochs", "0", "--wire-format", "--live")                # measured in the run: 4 B per sample, read once
     assert d["roofline"]["traffic_source"].startswith("measured in this run")
     assert 1.0 <= d["roofline"]["traffic"] / d["config"]["bytes_per_gpu_per_step"] < 1.02
-    d = _run("--cpu-epochs", "0", "--wire-format", "--mode", "welch")
+    d = _run("--full", "--cpu-epochs", "0", "--wire-format", "--mode", "welch")
     assert "wire format" in d["config"]["workload"]
 
 
@@ -173,7 +186,7 @@ def test_bench_two_ranks_on_one_gpu_through_a_stand_in_rccl(built):
         from test_comm import _run_group   # own process group: a timeout must not leave the two ranks behind
         out = _run_group([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                           "--master-port", "29577", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "2",
-                          "--epochs", "2048", "--cpu-epochs", "32", *extra], 300, env, cwd=ROOT)
+                          "--epochs", "2048", "--full", "--cpu-epochs", "32", *extra], 300, env, cwd=ROOT)
         assert out.returncode == 0, _why(out.stderr)
         lines = [ln for ln in out.stdout.splitlines() if ln.strip().startswith("{")]
         assert len(lines) == 1, out.stdout[-2000:]
@@ -246,7 +259,7 @@ def test_bench_cfg4_rehearsal_four_self_launched_ranks_on_one_gpu(built, mode, s
     # be held by at most six processes at once.  The test is marked gpu_first so that this pytest process does not hold the device
     # beside them — tests/conftest.py — and the batch is large enough that the ~50 ms clock-ramp top-up is ~200 lock-step gathers.)
     n = 4
-    d = _self_launched(n, *mode, "--scaling", scaling, epochs="4096" if scaling == "weak" else str(4096 * n), cpu_epochs="32")
+    d = _self_launched(n, "--full", *mode, "--scaling", scaling, epochs="4096" if scaling == "weak" else str(4096 * n), cpu_epochs="32")
     assert d["n_gpus"] == n and d["scaling"] == scaling and d["config"]["epochs_per_gpu"] == 4096
     assert d["config"]["epochs_per_step_all_gpus"] == 4096 * n and d["config"]["streams_per_gpu"] == (2 if scaling == "strong" else 1)
     assert d["config"]["parallelism"].startswith(f"stream-sharded x{n}") and "crn_comm_" in d["config"]["parallelism"]

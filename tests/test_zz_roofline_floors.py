@@ -1,6 +1,7 @@
 """north_star's ">= 70 % of the HBM-read roofline" as a tested property: bench.py on the driver's shape (`--steps 20 --warmup 5`, default
 batch) must reach the floors of tests/perf_floors.py on every leg — headline, SURVEY §8(d) cfgH's 2 GiB batch on one and on two streams,
-the unpruned kernel, and the cfg1 / cfg2 / cfg3 configurations — and the kernel time must fit inside the step time.
+the unpruned kernel (those three legs: with --full), and the cfg1 / cfg2 / cfg3 configurations — and the kernel time must fit inside the
+step time.
 
 (The file sorts last on purpose: the driver runs the GPU suite with -x, and a throughput gate should be the last thing that can stop it.)
 
@@ -74,10 +75,11 @@ def _check(name, d, seen, want):
 
 
 def test_headline_and_its_alt_legs_hold_their_floors(built):
-    """The driver's own command.  The headline also has to clear north_star's 70 % with the floor's margin on top."""
+    """The driver's own command, with --full for the alt legs.  The headline also has to clear north_star's 70 % with the floor's margin
+    on top."""
     want = {"main": pf.FLOORS["headline"], **{k: v for k, v in pf.FLOORS.items() if k.startswith("alt.")}}
     assert pf.FLOORS["headline"] >= pf.NORTH_STAR and pf.FLOORS["alt.cfgH_2GiB_batch"] >= pf.NORTH_STAR
-    d, seen = _best_of((), want)
+    d, seen = _best_of(("--full",), want)
     _record("headline", want, seen)
     _check("headline", d, seen, want)
     assert d["config"]["epochs_per_gpu"] == 28672 and d["config"]["fft_len"] == 4096 and d["steps"] == 20 and d["warmup"] == 5

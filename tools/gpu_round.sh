@@ -12,17 +12,17 @@ cd $R
 [ -x tools/ring_rate ] || make -C tests/harness ring_rate > /dev/null
 CRN_EVIDENCE_DIR=$O timeout 1500 python -m pytest tests -m gpu -q > $O/pytest_gpu.log 2>&1; echo "pytest exit $?" >> $O/pytest_gpu.log
 timeout 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1; echo "smoke exit $?" >> $O/smoke.log
-timeout 600 python bench.py > $O/bench_headline.json 2> $O/bench_headline.err
-timeout 300 python bench.py --fft 1024 > $O/bench_cfg1_1024.json 2> $O/bench_cfg1.err
-timeout 300 python bench.py --mode ref --cpu-epochs 0 > $O/bench_cfg3_ref512.json 2> $O/bench_cfg3.err
-timeout 300 python bench.py --mode welch --cpu-epochs 0 > $O/bench_cfg2_welch.json 2> $O/bench_cfg2.err
-timeout 300 python bench.py --mode welch --cpu-epochs 0 --frames 32 > $O/bench_cfg2_welch_K32.json 2> $O/bench_cfg2_K32.err
-timeout 300 python bench.py --mode scan --cpu-epochs 0 --force-collective > $O/bench_cfg4_scan_1rank.json 2> $O/bench_cfg4.err
-timeout 300 python bench.py --variant 2 --cpu-epochs 0 --no-alt > $O/bench_unpruned.json 2> $O/bench_unpruned.err
-timeout 300 python bench.py --fft 512 --cpu-epochs 0 > $O/bench_e512.json 2> $O/bench_e512.err
-timeout 300 python bench.py --fft 2048 --cpu-epochs 0 > $O/bench_e2048.json 2> $O/bench_e2048.err
+timeout 600 python bench.py --full > $O/bench_headline.json 2> $O/bench_headline.err
+timeout 300 python bench.py --full --fft 1024 > $O/bench_cfg1_1024.json 2> $O/bench_cfg1.err
+timeout 300 python bench.py --full --mode ref --cpu-epochs 0 > $O/bench_cfg3_ref512.json 2> $O/bench_cfg3.err
+timeout 300 python bench.py --full --mode welch --cpu-epochs 0 > $O/bench_cfg2_welch.json 2> $O/bench_cfg2.err
+timeout 300 python bench.py --full --mode welch --cpu-epochs 0 --frames 32 > $O/bench_cfg2_welch_K32.json 2> $O/bench_cfg2_K32.err
+timeout 300 python bench.py --full --mode scan --cpu-epochs 0 --force-collective > $O/bench_cfg4_scan_1rank.json 2> $O/bench_cfg4.err
+timeout 300 python bench.py --full --variant 2 --cpu-epochs 0 --no-alt > $O/bench_unpruned.json 2> $O/bench_unpruned.err
+timeout 300 python bench.py --full --fft 512 --cpu-epochs 0 > $O/bench_e512.json 2> $O/bench_e512.err
+timeout 300 python bench.py --full --fft 2048 --cpu-epochs 0 > $O/bench_e2048.json 2> $O/bench_e2048.err
 # the optional wire-format library (make SC16=1): one line, so that what is no longer in the shipped library is still seen to work
-[ -f cognitive-radio-network_amd/libcrnsense_sc16.so ] && timeout 300 python bench.py --wire-format --cpu-epochs 0 > $O/bench_wire_format_optional_library.json 2> $O/bench_wire_format.err
+[ -f cognitive-radio-network_amd/libcrnsense_sc16.so ] && timeout 300 python bench.py --full --wire-format --cpu-epochs 0 > $O/bench_wire_format_optional_library.json 2> $O/bench_wire_format.err
 # the driver's command shape; the N = 1 end of the strong-scaling curve and its per-GPU shares at N = 2 / 4 / 8 as ONE-GPU launches
 # (what one rank of the strong-scaled job runs: 1/N of the 8.75 GiB batch, two streams below 4 GiB) — the kernel-side scaling loss
 timeout 600 python3 bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_driver_shape.json 2> $O/bench_driver_shape.err
@@ -32,10 +32,10 @@ timeout 600 python3 bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_driver_sh
 # box's one GPU over the stand-in RCCL (real RCCL refuses two ranks per device; at most six processes may hold one GPU), weak and strong scaling
 export CRN_RCCL_LIB=$R/tests/harness/libfake_rccl_mp.so HIP_VISIBLE_DEVICES=0
 # (the N > 1 lines carry cpu_baseline: rank 0 measures it after the timed region with the default protocol)
-timeout 900 python3 bench.py --gpus 2 --steps 20 --warmup 5 --epochs 14336 > $O/bench_2ranks_one_gpu.json 2> $O/bench_2ranks_one_gpu.err
-timeout 900 python3 bench.py --gpus 4 --steps 20 --warmup 5 --epochs 7168 > $O/bench_4ranks_one_gpu.json 2> $O/bench_4ranks_one_gpu.err
-timeout 900 python3 bench.py --gpus 4 --steps 20 --warmup 5 --scaling strong > $O/bench_4ranks_one_gpu_strong.json 2> $O/bench_4ranks_one_gpu_strong.err
-timeout 900 python3 bench.py --gpus 4 --steps 20 --warmup 5 --mode scan --epochs 17920 > $O/bench_4ranks_one_gpu_scan.json 2> $O/bench_4ranks_one_gpu_scan.err
+timeout 900 python3 bench.py --full --gpus 2 --steps 20 --warmup 5 --epochs 14336 > $O/bench_2ranks_one_gpu.json 2> $O/bench_2ranks_one_gpu.err
+timeout 900 python3 bench.py --full --gpus 4 --steps 20 --warmup 5 --epochs 7168 > $O/bench_4ranks_one_gpu.json 2> $O/bench_4ranks_one_gpu.err
+timeout 900 python3 bench.py --full --gpus 4 --steps 20 --warmup 5 --scaling strong > $O/bench_4ranks_one_gpu_strong.json 2> $O/bench_4ranks_one_gpu_strong.err
+timeout 900 python3 bench.py --full --gpus 4 --steps 20 --warmup 5 --mode scan --epochs 17920 > $O/bench_4ranks_one_gpu_scan.json 2> $O/bench_4ranks_one_gpu_scan.err
 unset CRN_RCCL_LIB HIP_VISIBLE_DEVICES
 timeout 900 python tools/gpu_welch_spans.py > $O/welch_spans.txt 2>&1
 timeout 900 python tests/soak_gpu.py 20000 > $O/soak.txt 2>&1
