@@ -278,6 +278,44 @@ CRN_API int crn_sense_get_cfar_ex(crn_handle *h, crn_cfar_params_ex *params, int
  * CRN_ERR_ARG for arguments out of range and for a pfa too small to reach. */
 CRN_API int crn_cfar_alpha_ex(int32_t method, double pfa, int32_t frames_per_epoch, int32_t train, int32_t rank, double *alpha);
 
+/* -- emitter segments from the CFAR bin mask ---------------------------------------------------------------------------------
+ * The detector's back end: per epoch, the bit mask d[k] and the `spectrum` row P[k] (k in Z_N, circular like CFAR's training cells)
+ * become a short ordered list of segments and a noise estimate, on the device, for the whole batch in one launch.
+ *   1. closing   no bit set: no segments.  Otherwise every maximal circular run of zero bits of length <= merge_gap joins the closed
+ *                mask c (merge_gap = 0: c = d).
+ *   2. segments  the maximal circular runs of ones in c: bins (lo + i) mod N, 0 <= i < width; a segment may cross the wrap
+ *                (lo + width > N).  c all ones: one segment, lo = 0, width = N.
+ *   3. noise     before any filtering: noise_bins = bins with c = 0, noise_mean = the mean of P over them (0 when there are none).
+ *   4. filter    segments with width < min_width are dropped; n_found counts the rest; the first min(n_found, max_segments) by
+ *                ascending lo are stored (n_stored), so a wrap-crossing segment comes last.  Slots beyond n_stored are zero-filled:
+ *                a batch gives the same bytes however it is cut into launches.
+ *   5. stored    n_detected = set bits of d inside the segment; peak_bin = the absolute bin of the largest P (ties: the smallest i),
+ *                peak_power = that P; power = sum P; centroid = sum(i P) / sum(P), the power-weighted offset from lo in bins
+ *                (0 when the sum is 0).  Sums are accumulated in fp64 and rounded to fp32 once. */
+typedef struct crn_segment_params {
+  int32_t merge_gap, min_width, max_segments, reserved;
+} crn_segment_params;
+typedef struct crn_segment {
+  int32_t lo, width, peak_bin, n_detected;
+  float power, peak_power, centroid, reserved;
+} crn_segment; /* 32 bytes */
+typedef struct crn_segment_epoch {
+  int32_t n_found, n_stored, noise_bins;
+  float noise_mean;
+} crn_segment_epoch; /* 16 bytes */
+
+/* Enqueue the extraction on `stream` over n_epochs rows (device pointers):
+ *   d_bin_mask  [n_epochs][fft_len / 32]   as crn_sense_run_device_cfar writes it (8-byte aligned)
+ *   d_spectrum  [n_epochs][fft_len]        the `spectrum` output of the same launch (16-byte aligned)
+ *   d_epochs    [n_epochs]                 one header per epoch
+ *   d_segments  [n_epochs][max_segments]   or NULL: headers only (the count and the noise estimate)
+ * `h` supplies fft_len and the device, nothing else: the mask and rows may come from any source, the handle may be of any mode, with
+ * CFAR on or off.  Allocates nothing, keeps no state.  CRN_ERR_ARG for a NULL h, params, d_bin_mask, d_spectrum or d_epochs,
+ * merge_gap outside 0 .. fft_len - 1, min_width < 1, max_segments outside 1 .. 256, reserved != 0, n_epochs < 0 or a misaligned
+ * pointer.  n_epochs = 0 succeeds and launches nothing. */
+CRN_API int crn_segments_device(crn_handle *h, const uint32_t *d_bin_mask, const float *d_spectrum, int64_t n_epochs,
+                                const crn_segment_params *params, crn_segment_epoch *d_epochs, crn_segment *d_segments, void *stream);
+
 /* Allocate, now, the device scratch and pinned staging that crn_sense_run_host needs for up to
  * max_epochs dense epochs of full-length frames (and their per-bin spectra when want_spectrum != 0),
  * and load the kernels: a later crn_sense_run_host within that size allocates nothing.  An engine

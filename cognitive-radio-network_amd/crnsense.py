@@ -46,6 +46,7 @@ EXPORTS = [
     "crn_monitor_rows_device",
     "crn_sense_set_cfar", "crn_sense_get_cfar", "crn_sense_run_device_cfar", "crn_cfar_alpha",
     "crn_sense_set_cfar_ex", "crn_sense_get_cfar_ex", "crn_cfar_alpha_ex",
+    "crn_segments_device",
     "crn_comm_unique_id", "crn_comm_create", "crn_comm_local", "crn_comm_allgather", "crn_comm_gathered",
     "crn_comm_finish", "crn_comm_destroy", "crn_comm_local_addr", "crn_comm_wait", "crn_comm_info",
     "crn_last_error", "crn_abi_version", "crn_build_info",
@@ -88,6 +89,28 @@ class CfarParamsEx(C.Structure):
 
 
 CFAR_CA, CFAR_GO, CFAR_SO, CFAR_OS = 0, 1, 2, 3    # crn_cfar_method
+
+
+class SegmentParams(C.Structure):
+    """crn_segment_params (crn_segments_device)."""
+    _fields_ = [("merge_gap", C.c_int32), ("min_width", C.c_int32), ("max_segments", C.c_int32), ("reserved", C.c_int32)]
+
+
+class Segment(C.Structure):
+    """crn_segment: one stored segment, 32 bytes."""
+    _fields_ = [("lo", C.c_int32), ("width", C.c_int32), ("peak_bin", C.c_int32), ("n_detected", C.c_int32),
+                ("power", C.c_float), ("peak_power", C.c_float), ("centroid", C.c_float), ("reserved", C.c_float)]
+
+
+class SegmentEpoch(C.Structure):
+    """crn_segment_epoch: one epoch's header, 16 bytes."""
+    _fields_ = [("n_found", C.c_int32), ("n_stored", C.c_int32), ("noise_bins", C.c_int32), ("noise_mean", C.c_float)]
+
+
+# numpy views of the two arrays crn_segments_device writes: np.frombuffer(bytes, SEGMENT_EPOCH_DTYPE), (.., SEGMENT_DTYPE).reshape(E, max_segments)
+SEGMENT_DTYPE = [("lo", "<i4"), ("width", "<i4"), ("peak_bin", "<i4"), ("n_detected", "<i4"),
+                 ("power", "<f4"), ("peak_power", "<f4"), ("centroid", "<f4"), ("reserved", "<f4")]
+SEGMENT_EPOCH_DTYPE = [("n_found", "<i4"), ("n_stored", "<i4"), ("noise_bins", "<i4"), ("noise_mean", "<f4")]
 CFAR_METHODS = {"ca": CFAR_CA, "go": CFAR_GO, "so": CFAR_SO, "os": CFAR_OS}
 
 
@@ -202,6 +225,8 @@ def lib():
         L.crn_sense_set_cfar_ex.argtypes = [C.c_void_p, C.POINTER(CfarParamsEx)]
         L.crn_sense_get_cfar_ex.argtypes = [C.c_void_p, C.POINTER(CfarParamsEx), C.POINTER(C.c_int32)]
         L.crn_cfar_alpha_ex.argtypes = [C.c_int32, C.c_double, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_double)]
+        L.crn_segments_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(SegmentParams), C.c_void_p, C.c_void_p,
+                                          C.c_void_p]
         L.crn_ingest_create.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]
         L.crn_ingest_push.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
         L.crn_ingest_flush.argtypes = [C.c_void_p]
@@ -314,6 +339,16 @@ def cfar_alpha(pfa, K, train, method="ca", rank=None):
         rank = cfar_os_rank(train) if m == CFAR_OS else 0
     check(lib().crn_cfar_alpha_ex(m, float(pfa), int(K), int(train), int(rank), C.byref(a)), "crn_cfar_alpha_ex")
     return a.value
+
+
+def segment_hz(lo, width, centroid, fft_len, fs, fc):
+    """(centre frequency, bandwidth) in Hz of a segment from crn_segments_device: the centre is the power centroid, at bin
+    lo + centroid; bin k lies at fc + k fs / N for k < N / 2 and at fc + (k - N) fs / N above, so a segment that crosses the wrap
+    (lo + width > N) comes out as one emitter around fc.  The bandwidth is width bins."""
+    k = (float(lo) + float(centroid)) % fft_len
+    if k >= fft_len / 2:
+        k -= fft_len
+    return fc + k * fs / fft_len, width * fs / fft_len
 
 
 def save_ann(cfg, path):
@@ -499,6 +534,14 @@ class Sensor:
         o = Out(**{k: (v or None) for k, v in out_ptrs.items()})
         check(lib().crn_sense_run_device_cfar(self._h, iq_ptr, n_epochs, L, epoch_stride, C.byref(o), C.c_void_p(mask_ptr or None),
                                               C.c_void_p(band_bins_ptr or None), C.c_void_p(stream or None)), "crn_sense_run_device_cfar")
+
+    def segments_device(self, mask_ptr, spectrum_ptr, n_epochs, epochs_ptr, segments_ptr=0, merge_gap=0, min_width=1, max_segments=16, stream=0):
+        """Segments of n_epochs rows of a CFAR bin mask and the matching `spectrum` rows (device pointers): epochs_ptr [n_epochs]
+        SEGMENT_EPOCH_DTYPE, segments_ptr [n_epochs][max_segments] SEGMENT_DTYPE or 0 for the headers alone.  Only enqueues."""
+        q = SegmentParams(merge_gap=int(merge_gap), min_width=int(min_width), max_segments=int(max_segments), reserved=0)
+        check(lib().crn_segments_device(self._h, C.c_void_p(mask_ptr or None), C.c_void_p(spectrum_ptr or None), n_epochs, C.byref(q),
+                                        C.c_void_p(epochs_ptr or None), C.c_void_p(segments_ptr or None), C.c_void_p(stream or None)),
+              "crn_segments_device")
 
     def set_wire_full_scale(self, full_scale):
         _need_sc16("set_wire_full_scale")

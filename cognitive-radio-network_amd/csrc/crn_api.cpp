@@ -16,6 +16,7 @@
 #endif
 #include "crn_internal.h"
 #include "crn_kernels.h"
+#include "crn_segments.h"
 
 namespace crn {
 static thread_local std::string g_err;
@@ -102,6 +103,13 @@ struct crn_handle {
   int64_t t_issued = 0, t_collected = 0, t_dropped = 0;   // slots [t_collected, t_issued) are in flight (mod kTimedSlots)
   double kernel_ms = 0.0, kernel_ms_last = 0.0, kernel_ms_min = 0.0, kernel_ms_max = 0.0;
 };
+
+// crn_segments_device (crn_segments.hip) reads nothing else of a handle
+void crn::handle_geometry(crn_handle *h, int *fft_len, int *device) {
+  std::lock_guard<std::mutex> lk(h->tables_mu);
+  *fft_len = h->cfg.fft_len;
+  *device = h->device;
+}
 
 namespace {
 
