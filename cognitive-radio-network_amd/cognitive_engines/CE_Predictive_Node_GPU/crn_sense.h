@@ -316,6 +316,70 @@ typedef struct crn_segment_epoch {
 CRN_API int crn_segments_device(crn_handle *h, const uint32_t *d_bin_mask, const float *d_spectrum, int64_t n_epochs,
                                 const crn_segment_params *params, crn_segment_epoch *d_epochs, crn_segment *d_segments, void *stream);
 
+/* -- tracks: emitter segments linked across epochs ----------------------------------------------------------------------------
+ * One record per track, a transmitter's stay in one place of the band, from the two arrays crn_segments_device wrote.  A batch is
+ * n_epochs / epochs_per_stream streams of epochs_per_stream consecutive epochs in time order (crn_synth_cfg.n_streams); N = fft_len.
+ * Not a sequential tracker: tracks are the connected components of a graph, which every epoch can work on at once.
+ *   1. nodes    the stored segments: node (e, s), s < d_epochs[e].n_stored (segments beyond max_segments were never stored and are
+ *               not seen).  Epoch e belongs to stream e / epochs_per_stream; t = e % epochs_per_stream is its time in the stream.
+ *   2. links    nodes (e, a) and (e + d, b) of the same stream, 1 <= d <= max_miss + 1, are linked when
+ *                 ((lo_b - lo_a) mod N) < width_a + slack_bins  or  ((lo_a - lo_b) mod N) < width_b + slack_bins,
+ *               that is when, on the circle, the two bin intervals share a bin or the gap between them is smaller than slack_bins
+ *               (0: they must share a bin; 1: touching is enough).  Integers only; a wrap-crossing segment and a segment of width N
+ *               are no special cases.  Nodes of one epoch are never linked directly.
+ *   3. tracks   the connected components.  A component's root is its smallest node index e * max_segments + s: its earliest epoch,
+ *               there the lowest slot.  Two emitters that touch in some epoch (both linked to one segment of a neighbouring epoch)
+ *               are ONE track; a caller who wants them apart lowers slack_bins here or merge_gap in the extraction.
+ *   4. filter   n_epochs_hit = the number of distinct epochs with a member.  Components with n_epochs_hit < min_epochs are dropped
+ *               (an M-of-N confirmation: min_epochs = 2 removes single-epoch false alarms).  Per stream n_found counts the rest; they
+ *               are numbered 0, 1, ... by ascending root; the first min(n_found, max_tracks) are stored, the other slots zero-filled.
+ *   5. stored   first_t, last_t: the first and last time with a member; first_slot, last_slot: the lowest slot among the members in
+ *               that epoch (the two segments to look up for a drift); n_segments: members; each member m is placed at
+ *               off_m = ((lo_m - lo_root + N / 2) mod N) - N / 2 and covers off_m .. off_m + width_m - 1: lo_off and hi_off are the
+ *               smallest and largest offset covered; width_sum = sum of width_m (the mean width is width_sum / n_segments);
+ *               power_sum = sum of P_m, the members' power; peak_power = the largest of the members' peak_power (exact);
+ *               centre = (lo_root + sum(P_m (off_m + centroid_m)) / sum(P_m)) mod N, in bins (lo_root when the sum is 0; a value
+ *               that rounds to N is stored as 0); both sums in fp64, rounded to fp32 once.  flags: bit 0 when first_t <= max_miss
+ *               (the track may have begun before the batch), bit 1 when last_t >= epochs_per_stream - 1 - max_miss (it may go on
+ *               after it).  Nothing is carried from one call to the next.
+ *   6. labels   d_track_of[e][s] = the number of node (e, s)'s track within its stream (numbers >= max_tracks occur when the list was
+ *               truncated), -1 for empty slots and for members of dropped components. */
+typedef struct crn_track_params {
+  int32_t max_segments, epochs_per_stream, slack_bins, max_miss, min_epochs, max_tracks, reserved[2];
+} crn_track_params; /* 32 bytes */
+typedef struct crn_track {
+  int32_t first_t, last_t, first_slot, last_slot, n_epochs_hit, n_segments, lo_off, hi_off;
+  int64_t width_sum;
+  float power_sum, peak_power, centre;
+  int32_t flags, reserved[2];
+} crn_track; /* 64 bytes */
+typedef struct crn_track_stream {
+  int32_t n_found, n_stored, n_nodes, reserved; /* n_nodes: the stored segments of the stream */
+} crn_track_stream; /* 16 bytes */
+
+/* Bytes of device scratch crn_tracks_device needs for n_epochs epochs under `params` (of slack_bins only the sign is checked): needs no handle
+ * and no device.  Positive for valid arguments (also for n_epochs = 0), -1 for a NULL params, n_epochs < 0 or a parameter outside
+ * the ranges below, or when n_epochs x max_segments does not fit 31 bits. */
+CRN_API int64_t crn_tracks_workspace_bytes(int64_t n_epochs, const crn_track_params *params);
+
+/* Enqueue the linking on `stream` (device pointers):
+ *   d_epochs     [n_epochs]                             as crn_segments_device wrote them (16-byte aligned)
+ *   d_segments   [n_epochs][max_segments]               the same call's segments, the same max_segments (16-byte aligned)
+ *   d_streams    [n_epochs / epochs_per_stream]         one header per stream (16-byte aligned)
+ *   d_tracks     [n_epochs / epochs_per_stream][max_tracks]   (16-byte aligned)
+ *   d_track_of   [n_epochs][max_segments] int32, or NULL
+ *   d_workspace  workspace_bytes >= crn_tracks_workspace_bytes of scratch (8-byte aligned); its contents before and after mean nothing
+ * `h` supplies fft_len and the device, nothing else.  Only enqueues (seven small launches), allocates nothing, keeps no state; integer
+ * fields, flags, peak_power and the labels do not depend on the order the work ran in; power_sum and centre are summed with fp64
+ * atomic adds and may differ in the last bit between runs.  CRN_ERR_ARG, decided before any device call, for a NULL h, params,
+ * d_epochs, d_segments, d_streams, d_tracks or d_workspace; n_epochs < 0; max_segments outside 1 .. 256; epochs_per_stream < 1 or not
+ * dividing n_epochs; slack_bins outside 0 .. fft_len - 1; max_miss outside 0 .. 15; min_epochs < 1; max_tracks outside 1 .. 1024;
+ * reserved != 0; n_epochs x max_segments >= 2^31; a misaligned pointer; a workspace too small.  n_epochs = 0 succeeds and launches
+ * nothing. */
+CRN_API int crn_tracks_device(crn_handle *h, const crn_segment_epoch *d_epochs, const crn_segment *d_segments, int64_t n_epochs,
+                              const crn_track_params *params, crn_track_stream *d_streams, crn_track *d_tracks, int32_t *d_track_of,
+                              void *d_workspace, int64_t workspace_bytes, void *stream);
+
 /* Allocate, now, the device scratch and pinned staging that crn_sense_run_host needs for up to
  * max_epochs dense epochs of full-length frames (and their per-bin spectra when want_spectrum != 0),
  * and load the kernels: a later crn_sense_run_host within that size allocates nothing.  An engine

@@ -46,7 +46,7 @@ EXPORTS = [
     "crn_monitor_rows_device",
     "crn_sense_set_cfar", "crn_sense_get_cfar", "crn_sense_run_device_cfar", "crn_cfar_alpha",
     "crn_sense_set_cfar_ex", "crn_sense_get_cfar_ex", "crn_cfar_alpha_ex",
-    "crn_segments_device",
+    "crn_segments_device", "crn_tracks_workspace_bytes", "crn_tracks_device",
     "crn_comm_unique_id", "crn_comm_create", "crn_comm_local", "crn_comm_allgather", "crn_comm_gathered",
     "crn_comm_finish", "crn_comm_destroy", "crn_comm_local_addr", "crn_comm_wait", "crn_comm_info",
     "crn_last_error", "crn_abi_version", "crn_build_info",
@@ -111,6 +111,20 @@ class SegmentEpoch(C.Structure):
 SEGMENT_DTYPE = [("lo", "<i4"), ("width", "<i4"), ("peak_bin", "<i4"), ("n_detected", "<i4"),
                  ("power", "<f4"), ("peak_power", "<f4"), ("centroid", "<f4"), ("reserved", "<f4")]
 SEGMENT_EPOCH_DTYPE = [("n_found", "<i4"), ("n_stored", "<i4"), ("noise_bins", "<i4"), ("noise_mean", "<f4")]
+
+
+class TrackParams(C.Structure):
+    """crn_track_params (crn_tracks_device), 32 bytes."""
+    _fields_ = [("max_segments", C.c_int32), ("epochs_per_stream", C.c_int32), ("slack_bins", C.c_int32), ("max_miss", C.c_int32),
+                ("min_epochs", C.c_int32), ("max_tracks", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
+# numpy views of the two arrays crn_tracks_device writes: (.., TRACK_STREAM_DTYPE) [n_streams], (.., TRACK_DTYPE).reshape(n_streams, max_tracks)
+TRACK_DTYPE = [("first_t", "<i4"), ("last_t", "<i4"), ("first_slot", "<i4"), ("last_slot", "<i4"), ("n_epochs_hit", "<i4"), ("n_segments", "<i4"),
+               ("lo_off", "<i4"), ("hi_off", "<i4"), ("width_sum", "<i8"), ("power_sum", "<f4"), ("peak_power", "<f4"), ("centre", "<f4"),
+               ("flags", "<i4"), ("reserved", "<i4", (2,))]
+TRACK_STREAM_DTYPE = [("n_found", "<i4"), ("n_stored", "<i4"), ("n_nodes", "<i4"), ("reserved", "<i4")]
+TRACK_BEGAN_BEFORE, TRACK_GOES_ON = 1, 2      # crn_track.flags
 CFAR_METHODS = {"ca": CFAR_CA, "go": CFAR_GO, "so": CFAR_SO, "os": CFAR_OS}
 
 
@@ -227,6 +241,10 @@ def lib():
         L.crn_cfar_alpha_ex.argtypes = [C.c_int32, C.c_double, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_double)]
         L.crn_segments_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(SegmentParams), C.c_void_p, C.c_void_p,
                                           C.c_void_p]
+        L.crn_tracks_workspace_bytes.argtypes = [C.c_int64, C.POINTER(TrackParams)]
+        L.crn_tracks_workspace_bytes.restype = C.c_int64
+        L.crn_tracks_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(TrackParams), C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.c_void_p, C.c_int64, C.c_void_p]
         L.crn_ingest_create.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]
         L.crn_ingest_push.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
         L.crn_ingest_flush.argtypes = [C.c_void_p]
@@ -349,6 +367,29 @@ def segment_hz(lo, width, centroid, fft_len, fs, fc):
     if k >= fft_len / 2:
         k -= fft_len
     return fc + k * fs / fft_len, width * fs / fft_len
+
+
+def track_params(max_segments=16, epochs_per_stream=1, slack_bins=1, max_miss=0, min_epochs=1, max_tracks=64):
+    q = TrackParams(max_segments=int(max_segments), epochs_per_stream=int(epochs_per_stream), slack_bins=int(slack_bins), max_miss=int(max_miss),
+                    min_epochs=int(min_epochs), max_tracks=int(max_tracks))
+    q.reserved[0] = q.reserved[1] = 0
+    return q
+
+
+def tracks_workspace_bytes(n_epochs, max_segments=16, epochs_per_stream=None, max_miss=0, min_epochs=1, max_tracks=64):
+    """Bytes of device scratch Sensor.tracks_device needs (crn_tracks_workspace_bytes): no handle, no device."""
+    q = track_params(max_segments, n_epochs if epochs_per_stream is None else epochs_per_stream, 0, max_miss, min_epochs, max_tracks)
+    nb = lib().crn_tracks_workspace_bytes(int(n_epochs), C.byref(q))
+    if nb <= 0:
+        raise CrnError(f"crn_tracks_workspace_bytes: arguments out of range ({nb})")
+    return nb
+
+
+def track_hz(centre, width_sum, n_segments, fft_len, fs, fc):
+    """(centre frequency, mean bandwidth) in Hz of a track from crn_tracks_device: `centre` is already an absolute bin (the power-weighted
+    mean position of the members), the bandwidth is the members' mean width, width_sum / n_segments bins; the mapping of bins to hertz
+    is segment_hz's."""
+    return segment_hz(0, float(width_sum) / max(int(n_segments), 1), centre, fft_len, fs, fc)
 
 
 def save_ann(cfg, path):
@@ -542,6 +583,17 @@ class Sensor:
         check(lib().crn_segments_device(self._h, C.c_void_p(mask_ptr or None), C.c_void_p(spectrum_ptr or None), n_epochs, C.byref(q),
                                         C.c_void_p(epochs_ptr or None), C.c_void_p(segments_ptr or None), C.c_void_p(stream or None)),
               "crn_segments_device")
+
+    def tracks_device(self, epochs_ptr, segments_ptr, n_epochs, streams_ptr, tracks_ptr, workspace_ptr, workspace_bytes, track_of_ptr=0,
+                      max_segments=16, epochs_per_stream=None, slack_bins=1, max_miss=0, min_epochs=1, max_tracks=64, stream=0):
+        """Tracks from the two arrays segments_device wrote (device pointers): streams_ptr [n_streams] TRACK_STREAM_DTYPE, tracks_ptr
+        [n_streams][max_tracks] TRACK_DTYPE, track_of_ptr [n_epochs][max_segments] int32 or 0, workspace_ptr at least
+        tracks_workspace_bytes(...) of scratch; n_streams = n_epochs / epochs_per_stream (one stream when None).  Only enqueues."""
+        q = track_params(max_segments, n_epochs if epochs_per_stream is None else epochs_per_stream, slack_bins, max_miss, min_epochs, max_tracks)
+        check(lib().crn_tracks_device(self._h, C.c_void_p(epochs_ptr or None), C.c_void_p(segments_ptr or None), n_epochs, C.byref(q),
+                                      C.c_void_p(streams_ptr or None), C.c_void_p(tracks_ptr or None), C.c_void_p(track_of_ptr or None),
+                                      C.c_void_p(workspace_ptr or None), int(workspace_bytes), C.c_void_p(stream or None)),
+              "crn_tracks_device")
 
     def set_wire_full_scale(self, full_scale):
         _need_sc16("set_wire_full_scale")

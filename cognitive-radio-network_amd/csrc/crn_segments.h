@@ -1,5 +1,5 @@
-// crn_segments.h — emitter segments from the CFAR bin mask (crn_segments_device, include/crn_sense.h): what crn_segments.hip
-// needs from the rest of the library, and nothing the sensing kernels include.
+// crn_segments.h — emitter segments from the CFAR bin mask and their tracks (crn_segments_device, crn_tracks_device,
+// include/crn_sense.h): what crn_segments.hip and crn_tracks.hip need from the rest of the library, and nothing the sensing kernels include.
 #ifndef CRN_SEGMENTS_H
 #define CRN_SEGMENTS_H
 #include "../../include/crn_sense.h"

@@ -1,0 +1,69 @@
+"""The track-linking kernels (csrc/crn_tracks.hip) keep everything in registers and a little LDS: no scratch.  Like
+tests/test_segments_resources.py this test compiles the file itself, for gfx950, with the library's flags and
+-Rpass-analysis=kernel-resource-usage, and pins the scratch and the LDS of every kernel in it; the same compilation's assembly shows
+that the union hooks with one vector compare-and-swap, that the fp64 sums are native vector atomic adds (no compare-and-swap loop),
+and that nothing but vector instructions writes memory."""
+import os
+import re
+import subprocess
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "cognitive-radio-network_amd", "csrc")
+HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+
+# LDS bytes per workgroup: link holds two lists of 256 (lo, width) pairs, gather the 256 roots of its epoch, scan two words per wave
+LDS = {"tracks_init_kernel": 0, "tracks_link_kernel": 4096, "tracks_gather_kernel": 1024, "tracks_count_kernel": 0,
+       "tracks_scan_kernel": 128, "tracks_emit_kernel": 0, "tracks_labels_kernel": 0}
+
+
+@pytest.fixture(scope="module")
+def compiled(tmp_path_factory):
+    out = tmp_path_factory.mktemp("tracks") / "crn_tracks.s"
+    mk = open(os.path.join(CSRC, "Makefile")).read()
+    flags = re.search(r"^FLAGS\s*:=\s*(.*?)\n(?=#)", mk, re.S | re.M).group(1).replace("\\\n", " ").replace("$(ARCH)", "gfx950").split()
+    r = subprocess.run([HIPCC, *flags, "--cuda-device-only", "-Wno-unused-command-line-argument", "-Rpass-analysis=kernel-resource-usage",
+                        "-S", "-o", str(out), os.path.join(CSRC, "crn_tracks.hip")], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-2000:]
+    return r.stderr, open(out).read()
+
+
+def _kernels(txt):
+    out = {}
+    for b in re.split(r"remark: [^\n]*Function Name: ", txt)[1:]:
+        name = b.split('\n')[0].strip().split(' ')[0]
+
+        def g(k):
+            m = re.search(k + r": (\d+)", b)
+            return int(m.group(1)) if m else None
+        dem = subprocess.run(['c++filt', name], capture_output=True, text=True).stdout.strip()
+        short = re.search(r"(tracks_\w+_kernel)", dem)
+        out[short.group(1) if short else dem] = {"scratch": g(r"ScratchSize \[bytes/lane\]"), "occ": g(r"Occupancy \[waves/SIMD\]"),
+                                                 "vgprs": g(r" VGPRs"), "lds": g(r"LDS Size \[bytes/block\]")}
+    return out
+
+
+def test_track_kernels_do_not_spill(compiled):
+    ks = _kernels(compiled[0])
+    assert sorted(ks) == sorted(LDS), sorted(ks)
+    bad = {n: k for n, k in ks.items() if k["scratch"] != 0 or k["occ"] is None or k["occ"] < 1}
+    assert not bad, bad
+    assert {n: k["lds"] for n, k in ks.items()} == LDS
+
+
+def test_memory_is_written_by_vector_instructions_only(compiled):
+    asm = "\n".join(ln.split(";")[0] for ln in compiled[1].splitlines())
+    ops = set(re.findall(r"^\s+([a-z][a-z0-9_]+)\s", asm, re.M))
+    scalar_mem = {o for o in ops if o.startswith("s_") and any(w in o for w in ("store", "atomic", "dcache"))}
+    assert not scalar_mem, scalar_mem
+    assert not {o for o in ops if o.startswith("scratch_")}
+    assert len(re.findall(r"global_atomic_cmpswap", asm)) == 1          # the hook of the union; every other atomic is a native one
+    assert len(re.findall(r"global_atomic_add_f64", asm)) == 2          # power_sum and the centre's moment
+
+
+def test_the_file_is_in_every_library_flavour():
+    mk = open(os.path.join(CSRC, "Makefile")).read()
+    assert re.search(r"^H_SRCS\s*:=.*\bcrn_segments\.hip crn_tracks\.hip\b", mk, re.M)
+    assert re.search(r"^REST\s*:=.*crn_tracks\.hip\.o", mk, re.M)
+    assert re.search(r"^ASM_SRC \?= \$\(HERE\)crn_kernels\.hip$", mk, re.M)
