@@ -24,13 +24,6 @@
 
 static_assert(CRN_COMM_ID_BYTES == NCCL_UNIQUE_ID_BYTES, "crn_sense.h carries the size of ncclUniqueId");
 
-#define HIP_TRY(expr)                                                                      \
-  do {                                                                                     \
-    hipError_t _e = (expr);                                                                \
-    if (_e != hipSuccess)                                                                  \
-      return crn::fail(CRN_ERR_DEVICE, std::string(#expr) + ": " + hipGetErrorString(_e)); \
-  } while (0)
-
 namespace {
 
 struct Rccl {

@@ -171,9 +171,9 @@ CRN_DEV void epoch_close(FrameCtx<C> &c, const SenseParams &p, long long epoch_b
   const unsigned tab_off = c.lds_base + (unsigned)((G::GROUPS * C::NBUF * G::GROUP_CPLX + 16 * R3) * sizeof(cx));
   const unsigned gb_off = c.lds_base + (unsigned)grp * (unsigned)(C::NBUF * G::GROUP_CPLX * sizeof(cx));
   const lds_i32 *tab = reinterpret_cast<const lds_i32 *>(tab_off);
-  const lds_f32 *thr = reinterpret_cast<const lds_f32 *>(tab_off + 416 * 4);
-  const lds_f64 *w_ih = reinterpret_cast<const lds_f64 *>(tab_off + 544 * 4);  // [5][6]
-  const lds_f64 *w_ho = reinterpret_cast<const lds_f64 *>(tab_off + 604 * 4);  // [6][4]
+  const lds_f32 *thr = reinterpret_cast<const lds_f32 *>(tab_off + kTabThresh * 4);
+  const lds_f64 *w_ih = reinterpret_cast<const lds_f64 *>(tab_off + kTabWih * 4);  // [5][6]
+  const lds_f64 *w_ho = reinterpret_cast<const lds_f64 *>(tab_off + kTabWho * 4);  // [6][4]
   lds_f32 *spec = reinterpret_cast<lds_f32 *>(gb_off);    // N + N/16 floats
   lds_f32 *featl = spec + spec_phys(N);                   // CRN_MAX_BANDS floats (LDS path)
   constexpr int TEAM = G::TEAM;
@@ -242,7 +242,7 @@ CRN_DEV void epoch_close(FrameCtx<C> &c, const SenseParams &p, long long epoch_b
   } else if constexpr ((C::OPT & kRegBands) != 0) {
     // Band sums straight from the accumulator registers: no LDS image of the spectrum, no barrier
     // before it (nothing aliases the exchange buffers) and none after the decision.  Thread bins are
-    // base_j + 256 d; the host cut the band plan at the 256-bin rows (crn_api.cpp), so each entry is
+    // base_j + 256 d; the host cut the band plan at the 256-bin rows (crn_tables.cpp), so each entry is
     // (row d, band, [lo, hi) in the row): masked add over j, DPP team sum, lane `band` keeps it.
     // LDS round trips are what this block avoids (an LDS read here queues behind the exchange
     // traffic of the CU's other waves: measured ~500 ticks each): the entries come through the
@@ -266,14 +266,14 @@ CRN_DEV void epoch_close(FrameCtx<C> &c, const SenseParams &p, long long epoch_b
     };
     constexpr int kFirst = next_live(-1);
     float fsum = 0.f;
-    typename SWords<CAP>::T ent_next = s_load_row<CAP, (512 + kFirst * CAP) * 4>(p.band_tab);
+    typename SWords<CAP>::T ent_next = s_load_row<CAP, (kTabRowEntries + kFirst * CAP) * 4>(p.band_tab);
     static_for<R3>([&](auto dc) {
       constexpr int d = decltype(dc)::value;
       if constexpr (row_live(d)) {
         typename SWords<CAP>::T ent = ent_next;
         s_wait_row(ent);
         constexpr int dn = next_live(d);
-        if constexpr (dn < R3) ent_next = s_load_row<CAP, (512 + dn * CAP) * 4>(p.band_tab);
+        if constexpr (dn < R3) ent_next = s_load_row<CAP, (kTabRowEntries + dn * CAP) * 4>(p.band_tab);
 #pragma unroll
         for (int e = 0; e < CAP; e++) {
           const int w = ent[e];
@@ -344,8 +344,8 @@ CRN_DEV void epoch_close(FrameCtx<C> &c, const SenseParams &p, long long epoch_b
       pre_s0 = tab[t];
       pre_s1 = tab[t + 1];
       if (pre_s1 > pre_s0) {
-        pre_lo = tab[96 + pre_s0];
-        pre_hi = tab[256 + pre_s0];
+        pre_lo = tab[kTabSegLo + pre_s0];
+        pre_hi = tab[kTabSegHi + pre_s0];
       }
     }
     if constexpr (G::XWAVE) __syncthreads();
@@ -414,8 +414,8 @@ CRN_DEV void epoch_close(FrameCtx<C> &c, const SenseParams &p, long long epoch_b
       const bool first = b == t;  // this lane's first band: descriptor fetched before the barriers
       const int s0 = first ? pre_s0 : tab[b], s1 = first ? pre_s1 : tab[b + 1];
       for (int sg = s0; sg < s1; sg++) {
-        int k = (first && sg == s0) ? pre_lo : tab[96 + sg];
-        const int hi = (first && sg == s0) ? pre_hi : tab[256 + sg];
+        int k = (first && sg == s0) ? pre_lo : tab[kTabSegLo + sg];
+        const int hi = (first && sg == s0) ? pre_hi : tab[kTabSegHi + sg];
         while (k < hi && (k & 15) != 0) sum += spec[spec_phys(k++)];
         if (k + 16 <= hi) {
           // whole blocks up to the next row boundary, whole rows, whole blocks after them
@@ -620,8 +620,8 @@ CRN_DEV void epoch_close(FrameCtx<C> &c, const SenseParams &p, long long epoch_b
       for (int b = t; b < p.n_bands; b += T) {
         int n = 0;
         for (int sg = tab[b], s1 = tab[b + 1]; sg < s1; sg++) {
-          const int hi = tab[256 + sg];
-          for (int k = tab[96 + sg]; k < hi;) {
+          const int hi = tab[kTabSegHi + sg];
+          for (int k = tab[kTabSegLo + sg]; k < hi;) {
             const int w = k >> 5, e = hi < ((w + 1) << 5) ? hi : ((w + 1) << 5);
             unsigned m = mk32[w] >> (k & 31);
             if (e - k < 32) m &= (1u << (e - k)) - 1u;

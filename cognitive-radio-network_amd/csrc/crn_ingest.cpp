@@ -39,13 +39,6 @@
 #endif
 #include "crn_internal.h"
 
-#define HIP_TRY(expr)                                                                      \
-  do {                                                                                     \
-    hipError_t _e = (expr);                                                                \
-    if (_e != hipSuccess)                                                                  \
-      return crn::fail(CRN_ERR_DEVICE, std::string(#expr) + ": " + hipGetErrorString(_e)); \
-  } while (0)
-
 namespace {
 
 struct Slot {
@@ -138,13 +131,6 @@ struct crn_ingest {
 };
 
 constexpr int kCalibMaxEpochs = 4096;      // crn_noise_floor_device uses at most this many
-
-// defined in crn_api.cpp
-extern "C" int crn_sense_cfg_of(crn_handle *h, crn_cfg *out);
-extern "C" int crn_sense_ring_count(crn_handle *h, int delta);
-extern "C" int crn_sense_warm_stream(crn_handle *h, void *stream);
-extern "C" int crn_sense_run_device_any(crn_handle *h, const void *d_iq, int32_t bytes_per_sample, int64_t n_epochs, int32_t samples_per_frame,
-                                        int64_t epoch_stride, const crn_out *d_out, void *stream);
 
 namespace {
 

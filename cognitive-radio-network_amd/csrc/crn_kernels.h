@@ -1,4 +1,4 @@
-// crn_kernels.h — kernel parameter blocks shared by crn_kernels.hip and crn_api.cpp (internal).
+// crn_kernels.h — kernel parameter blocks shared by the kernel translation units and the host code that fills them (internal).
 #ifndef CRN_KERNELS_H
 #define CRN_KERNELS_H
 
@@ -9,6 +9,16 @@ namespace crn {
 
 constexpr int kBandTabWords = 656;   // SenseParams::band_tab, copied to LDS by every workgroup
 constexpr int kRowEntryWords = 32;   // row-entry slots of the register-resident band sums: 32 / R3 per row
+// band_tab's layout, word offset and length of every region (written by crn_tables.cpp, thresholds and weights rewritten in place by
+// crn_updates.cpp, read from LDS by crn_epoch_close.h)
+constexpr int kTabSegBegin = 0, kTabSegBeginWords = 96;              // band_seg_begin: n_bands + 1 words
+constexpr int kTabSegLo = 96, kTabSegHi = 256, kTabSegWords = 160;   // seg_lo, seg_hi: one word per segment each
+constexpr int kTabThresh = 416, kTabThreshWords = 80;                // thresh (float bits), one per band
+constexpr int kTabRowEntries = 512;   // kRowEntryWords entries band<<18 | lo<<9 | hi, 32 / R3 slots per 256-bin row, 0 = unused (only when n_row_entries > 0)
+constexpr int kTabWih = 544, kTabWihWords = 60, kTabWho = 604, kTabWhoWords = 48;   // ann_w_ih as 30 doubles, ann_w_ho as 24 doubles
+static_assert(kTabSegBegin + kTabSegBeginWords <= kTabSegLo && kTabSegLo + kTabSegWords <= kTabSegHi && kTabSegHi + kTabSegWords <= kTabThresh &&
+              kTabThresh + kTabThreshWords <= kTabRowEntries && kTabRowEntries + kRowEntryWords <= kTabWih && kTabWih % 2 == 0 &&
+              kTabWih + kTabWihWords <= kTabWho && kTabWho + kTabWhoWords <= kBandTabWords, "band_tab: regions in order, disjoint, inside the table");
 
 enum { CRN_DECIDE_ANN_K = 0, CRN_DECIDE_THRESHOLD_K = 1, CRN_DECIDE_NONE_K = 2 };  // == crn_decide
 enum { CRN_CFAR_CA_K = 0, CRN_CFAR_GO_K = 1, CRN_CFAR_SO_K = 2, CRN_CFAR_OS_K = 3 };     // == crn_cfar_method
@@ -31,10 +41,7 @@ struct SenseParams {
   const float2 *tw1;       // [17][T]  W_N^{t a}, a = 0..16
   const float2 *tw2;       // [16][R3] W_T^{m c}
   const float *window;     // [N] or null
-  const int *band_tab;        // [kBandTabWords] packed copy of the tables below, staged into LDS by every workgroup:
-                              //   [0,96) band_seg_begin, [96,256) seg_lo, [256,416) seg_hi, [416,496) thresh (float bits),
-                              //   [512,544) row entries band<<18 | lo<<9 | hi, 32 / R3 slots per 256-bin row, 0 = unused
-                              //   (only when n_row_entries > 0), [544,604) ann_w_ih as 30 doubles, [604,652) ann_w_ho as 24 doubles
+  const int *band_tab;        // [kBandTabWords] packed copy of the tables below, staged into LDS by every workgroup (layout: kTab* above)
   const int *band_seg_begin;  // [n_bands + 1] into seg_lo/seg_hi (segments grouped by band)
   const int *seg_lo;
   const int *seg_hi;
@@ -51,7 +58,7 @@ struct SenseParams {
   unsigned acc_mask;       // bit j R3 + d set when some band holds a bin of the form a + 16 (g J + j) + 256 d, i.e. when accumulator
                            // register j R3 + d of some thread holds a band bin (N = 4096: bit d = the 256-bin row d)
   int deal_rounds;         // > 0: sense_kernel_dealt (one epoch per workgroup, its frames dealt to the lane groups, this many rounds of them);
-                           // set by the host for launches of a few epochs at N <= 1024 (crn_api.cpp)
+                           // set by the host for launches of a few epochs at N <= 1024 (crn_api.cpp: run_device_impl)
   float wire_unscale;      // wire-format launches: 1 / full scale (2^-15 by default) for a sum of magnitudes, its square for energies
   // outputs (device, nullable)
   float *features;

@@ -388,7 +388,7 @@ static hipError_t launch_dealt_win(const SenseParams &p, hipStream_t stream) {
 }
 
 // The register form of the epoch close applies to band plans the host could cut into row entries
-// (crn_api.cpp) when no per-bin spectrum is stored.
+// (crn_tables.cpp) when no per-bin spectrum is stored.
 static bool reg_bands(const SenseParams &p) { return p.n_row_entries > 0 && p.spectrum == nullptr; }
 // ... and pass 3 / the accumulate keep only the reference channel plan's registers when every band bin sits in one of them.
 template <int R3>

@@ -16,8 +16,6 @@
 #include "../../include/crn_sense.h"
 #include "crn_internal.h"
 
-extern "C" int crn_sense_cfg_of(crn_handle *h, crn_cfg *out);
-
 namespace crn {
 
 constexpr int kParams = 43;  // 5x5 input->hidden incl. bias row + 6x3 hidden->output incl. bias row
@@ -143,13 +141,6 @@ __global__ __launch_bounds__(kTrainThreads) void ann_train_kernel(const TrainPar
 }
 
 }  // namespace crn
-
-#define HIP_TRY(expr)                                                                          \
-  do {                                                                                         \
-    hipError_t _e = (expr);                                                                    \
-    if (_e != hipSuccess)                                                                      \
-      return crn::fail(CRN_ERR_DEVICE, std::string(#expr) + ": " + hipGetErrorString(_e));     \
-  } while (0)
 
 extern "C" int crn_ann_train_device(crn_handle *h, const crn_train_cfg *tc, const float *d_features,
                                     const int32_t *d_labels, int64_t n, double w_ih[5][6], double w_ho[6][4],

@@ -1,4 +1,4 @@
-// TEST INFRASTRUCTURE: live updates of a handle against launches from another thread, without a GPU.  csrc/crn_api.cpp + crn_cfg.cpp +
+// TEST INFRASTRUCTURE: live updates of a handle against launches from another thread, without a GPU.  The handle's host files (Makefile: API_SRCS) +
 // crn_ingest.cpp as they are over tests/harness/fake_hip; built twice — ThreadSanitizer and AddressSanitizer (Makefile).
 //   thread A (the "CE thread"): pushes packets through a real ingest ring, whose launcher thread calls crn_sense_run_device
 //   thread B (the handle's owner): crn_sense_set_bands (same number of bands), crn_sense_set_thresholds, crn_sense_set_ann in a loop

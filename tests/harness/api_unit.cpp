@@ -1,6 +1,6 @@
-// TEST INFRASTRUCTURE: the host logic of csrc/crn_api.cpp on a machine without a GPU — table building (twiddles, window, the band plan
+// TEST INFRASTRUCTURE: the host logic of csrc/crn_api.cpp, crn_tables.cpp, crn_updates.cpp, crn_cfar.cpp and crn_api_sc16.cpp without a GPU — table building (twiddles, window, the band plan
 // in its packed LDS form, row entries, accumulator mask), launch geometry (every epoch group handed to exactly one workgroup, whatever
-// the batch size, FFT size and CU count), argument checks, live updates, counters.  crn_api.cpp and crn_cfg.cpp are compiled as they
+// the batch size, FFT size and CU count), argument checks, live updates, counters.  Those files and crn_cfg.cpp are compiled as they
 // are against tests/harness/fake_hip (device memory = host memory, so the tables a launch would read can be read back here); the
 // kernels' launch functions are stand-ins that record the parameter block they were handed.  Nothing of this is linked into the product.
 #include <hip/hip_runtime.h>
@@ -18,9 +18,9 @@
 #include "../../cognitive-radio-network_amd/csrc/crn_kernels.h"
 
 std::atomic<long long> g_fake_gpu_latency_ns{0};
-extern "C" int crn_sense_ring_count(crn_handle *h, int delta);   // internal (crn_ingest.cpp uses it)
+extern "C" int crn_sense_ring_count(crn_handle *h, int delta);   // internal (csrc/crn_internal.h; crn_ingest.cpp uses it)
 
-// ---- stand-ins for csrc/crn_kernels.hip (what crn_api.cpp calls) ---------------------------------------------------
+// ---- stand-ins for csrc/crn_kernels.hip (what the host files call) -------------------------------------------------
 namespace {
 crn::SenseParams g_last;
 int g_last_fft = 0, g_last_variant = -1, g_launches = 0;

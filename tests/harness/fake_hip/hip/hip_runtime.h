@@ -63,7 +63,7 @@ inline hipError_t hipEventSynchronize(hipEvent_t e) {
   return hipSuccess;
 }
 
-// What csrc/crn_api.cpp needs beyond the ring's calls (tests/harness/api_unit.cpp: table building and launch geometry on the host).
+// What csrc/crn_api.cpp, crn_tables.cpp and crn_updates.cpp need beyond the ring's calls (tests/harness/api_unit.cpp: table building and launch geometry on the host).
 // The "device" has g_fake_hip_cus compute units; kernels are the test's own stand-ins for the launch_* functions.
 #define HIP_VERSION_MAJOR 7
 #define HIP_VERSION_MINOR 2
@@ -80,7 +80,7 @@ inline hipError_t hipDeviceGetAttribute(int *v, int attr, int) {
   *v = attr == hipDeviceAttributeMultiprocessorCount ? g_fake_hip_cus : attr == hipDeviceAttributeMaxSharedMemoryPerBlock ? g_fake_hip_lds_bytes : 0;
   return hipSuccess;
 }
-// stream capture: a test marks a stream as capturing (crn_api.cpp refuses updates on it)
+// stream capture: a test marks a stream as capturing (crn_updates.cpp refuses updates on it)
 enum hipStreamCaptureStatus { hipStreamCaptureStatusNone = 0, hipStreamCaptureStatusActive = 1 };
 inline std::atomic<void *> g_fake_hip_capturing_stream{nullptr};
 inline hipError_t hipStreamIsCapturing(hipStream_t s, hipStreamCaptureStatus *st) {

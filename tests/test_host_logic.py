@@ -47,7 +47,7 @@ def test_butterfly_algebra_on_the_host(built):
 
 
 def test_api_host_logic_tables_and_launch_geometry(built):
-    """tests/harness/api_unit.cpp: csrc/crn_api.cpp + crn_cfg.cpp as they are, over the host-only HIP stand-in (device memory is host
+    """tests/harness/api_unit.cpp: the handle's host files (csrc/crn_api.cpp, crn_tables.cpp, ..: API_SRCS of the harness Makefile) as they are, over the host-only HIP stand-in (device memory is host
     memory; the launch functions record the parameter block): the twiddle tables against long-double values, the Hann table and its
     w[n] + w[n + N/2] = 1 symmetry, the packed band table and its row entries rebuilt into the plan bin by bin, the accumulator mask
     against the layout rule, every epoch group handed to exactly one workgroup for 5 CU counts x 4 sizes x 4 K x 21 batch sizes (and
@@ -62,7 +62,7 @@ def test_api_host_logic_tables_and_launch_geometry(built):
 
 def test_live_updates_against_the_ring_launcher_thread(built):
     """tests/harness/api_race_unit.cpp: one thread pushes packets through a real ingest ring (whose launcher thread launches through
-    the handle) while another swaps the band plan (same number of bands) and the thresholds in a loop — crn_api.cpp + crn_ingest.cpp
+    the handle) while another swaps the band plan (same number of bands) and the thresholds in a loop — crn_api.cpp, crn_updates.cpp + crn_ingest.cpp
     as they are over the host-only HIP stand-in.  Every launch must see one plan, whole; crn_sense_destroy is refused while the ring is
     attached.  ThreadSanitizer build, then AddressSanitizer + UBSan (a launch that kept a pointer into a freed table slab is a report).
     (Sensitivity, checked by hand in round 4: with the lock taken out of run_device_impl the same program draws 25 ThreadSanitizer reports.)"""

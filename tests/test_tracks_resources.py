@@ -65,5 +65,8 @@ def test_memory_is_written_by_vector_instructions_only(compiled):
 def test_the_file_is_in_every_library_flavour():
     mk = open(os.path.join(CSRC, "Makefile")).read()
     assert re.search(r"^H_SRCS\s*:=.*\bcrn_segments\.hip crn_tracks\.hip\b", mk, re.M)
-    assert re.search(r"^REST\s*:=.*crn_tracks\.hip\.o", mk, re.M)
+    # the host objects every flavour shares are derived from H_SRCS, and each flavour links them
+    assert re.search(r"^REST\s*:=.*\$\(O\)/%\.o.*\$\(H_SRCS\)", mk, re.M)
+    for objs in ("OBJS", "OBJS_AB", "OBJS_SC", "OBJS_PL"):
+        assert re.search(r"^%s\s*:=.*(\$\(REST\)|\$\(H_SRCS:%%=\$\(O\)/%%\.o\))" % objs, mk, re.M), objs
     assert re.search(r"^ASM_SRC \?= \$\(HERE\)crn_kernels\.hip$", mk, re.M)
