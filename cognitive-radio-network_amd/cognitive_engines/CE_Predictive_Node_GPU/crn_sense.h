@@ -380,6 +380,77 @@ CRN_API int crn_tracks_device(crn_handle *h, const crn_segment_epoch *d_epochs, 
                               const crn_track_params *params, crn_track_stream *d_streams, crn_track *d_tracks, int32_t *d_track_of,
                               void *d_workspace, int64_t workspace_bytes, void *stream);
 
+/* -- tracks carried across batches ---------------------------------------------------------------------------------------------
+ * crn_tracks_device knows one batch.  Here a sequence of calls covers, for every stream of the batch, the times
+ * t_start .. t_start + epochs_per_stream - 1: global epoch counts per stream since the call with t_start = 0.  T = t_start +
+ * epochs_per_stream, H = max_miss + 1, N = fft_len.
+ * What the caller sees.  Take the link graph of crn_tracks_device (its steps 1-2) over all epochs 0 .. T - 1 of the stream.  After a call
+ * a component is OPEN when last_t >= T - 1 - max_miss and flush == 0, otherwise CLOSED.  Every component is reported exactly once, by
+ * the call in which it becomes closed, with the fields crn_tracks_device would give for the whole stream in one batch of T epochs
+ * (global first_t / last_t; flag bit 0 when first_t <= max_miss; bit 1 when last_t >= T - 1 - max_miss, which only a record closed by
+ * `flush` can have), apart from the two exceptions below.  Within a call the closed components with n_epochs_hit >= min_epochs are
+ * numbered by ascending root (first_t, first_slot); the first max_tracks are stored, the other slots zero-filled; n_found counts all.
+ * The carry is opaque device memory written by the call, per stream: T; the TAIL, the stored (lo, width) lists of the epochs
+ * T - H .. T - 1 (fewer before H epochs were seen), each segment with the position of the open track it belongs to; and the OPEN
+ * TRACKS in ascending root order, each with its root (t, slot), lo_root, last (t, slot), hits, n_segments, lo_off, hi_off, width_sum,
+ * power and moment in fp64, peak and a `merged` bit.  Every tail segment belongs to an open track and every open track has a tail
+ * segment, so at most H x max_segments tracks are open per stream: the carry is sized for that and nothing overflows.
+ * One call (the incremental rule):
+ *   1. nodes    the open tracks (in carry order), then the tail segments, then the new stored segments by (t, slot).
+ *   2. joins    each tail segment is joined to its open track.
+ *   3. links    step 2's condition of crn_tracks_device between any tail or new segment and any NEW segment 1 .. H epochs later.
+ *   4. tracks   the connected components; the root is the smallest node in the order of item 1, so a component holding carried tracks
+ *               keeps the earliest carried root.
+ *   5. fresh    a component without a carried track accumulates as in crn_tracks_device.
+ *   6. carried  a component rooted at carried track A starts from A's accumulators.  Every further carried track B adds itself re-based
+ *               by delta = ((lo_root_B - lo_root_A + N / 2) mod N) - N / 2: lo_off_B + delta and hi_off_B + delta enter the min / max,
+ *               moment_B + delta power_B is added, counts and sums add, peak and last (t, lowest slot) take the maximum.
+ *   7. new      new segments add with `off` relative to lo_root_A; tail segments add nothing (they are already counted).
+ *   8. hits     distinct NEW epochs with a member add to the hits.
+ *   9. merged   when two or more carried tracks end in one component the epochs they shared cannot be known: the merged bit is set and
+ *               stays set, hits becomes min(sum, last_t - first_t + 1), and the record carries flag bit 2 (n_epochs_hit is an upper
+ *               bound).
+ *  10. split    open tracks go to the new carry in ascending root order, the new tail is written, closed components are emitted.
+ * The two exceptions to whole-batch equality: (a) records with bit 2: n_epochs_hit lies between the true count and the span, and
+ * min_epochs is applied to the bound; every other field is the whole-batch value.  (b) Re-basing by delta is exact only while a track
+ * covers less than N / 2 bins (hi_off - lo_off < N / 2); wider tracks get the values the rule gives, and the rule is the definition. */
+typedef struct crn_track_carry_stream {
+  int32_t n_found, n_stored, n_nodes;              /* closed by this call; stored segments of this call's epochs */
+  int32_t n_open, n_open_found, n_open_stored;     /* carried on; of those hits >= min_epochs; written to d_open */
+  int32_t status, reserved;                        /* bit 0: the carry did not match and was taken as empty */
+} crn_track_carry_stream; /* 32 bytes */
+#define CRN_TRACK_BEGAN_BEFORE 1     /* crn_track.flags */
+#define CRN_TRACK_GOES_ON 2
+#define CRN_TRACK_HITS_UPPER_BOUND 4 /* crn_tracks_carry_device only */
+
+/* Bytes of the carry for n_streams streams under `params` (max_segments and max_miss decide; the other fields are only checked): needs
+ * no handle and no device.  Positive for valid arguments (also for n_streams = 0), -1 as crn_tracks_workspace_bytes (a NULL params,
+ * n_streams < 0, a parameter out of range). */
+CRN_API int64_t crn_tracks_carry_bytes(int64_t n_streams, const crn_track_params *params);
+/* Bytes of device scratch crn_tracks_carry_device needs for n_epochs epochs under `params`; -1 as crn_tracks_workspace_bytes, or when
+ * (n_epochs + 2 (max_miss + 1) n_epochs / epochs_per_stream) x max_segments does not fit 31 bits. */
+CRN_API int64_t crn_tracks_carry_workspace_bytes(int64_t n_epochs, const crn_track_params *params);
+
+/* Enqueue one call of the sequence on `stream` (device pointers; d_epochs, d_segments, d_workspace as for crn_tracks_device):
+ *   d_carry     carry_bytes >= crn_tracks_carry_bytes(n_epochs / epochs_per_stream, params), 16-byte aligned: read, then rewritten
+ *   d_streams   [n_streams]               one crn_track_carry_stream per stream (16-byte aligned)
+ *   d_tracks    [n_streams][max_tracks]   the records this call closed (16-byte aligned)
+ *   d_open      [n_streams][max_tracks]   or NULL: the open tracks as they stand after the call, flag bit 1 set; only those with
+ *               hits >= min_epochs, the first max_tracks by ascending root, the rest zero-filled (n_open_stored is 0 for NULL)
+ * t_start = 0 starts afresh: the carry's previous contents mean nothing and the call initialises it; no reset function is needed.  For
+ * t_start > 0 each stream's carry holds a mark (max_segments, max_miss, fft_len and T); where it does not equal what the call expects
+ * (T = t_start) that stream is treated as having an empty carry and `status` bit 0 is set.  Every index read from the carry is clamped:
+ * a foreign buffer cannot cause an access outside the buffers.  slack_bins, min_epochs, max_tracks and epochs_per_stream may differ from
+ * call to call.  flush != 0 closes everything and leaves an empty carry with T advanced.  Only enqueues (seven small launches),
+ * allocates nothing, keeps no host state.  CRN_ERR_ARG, decided before any device call, for everything crn_tracks_device refuses (with
+ * the node count of crn_tracks_carry_workspace_bytes), t_start < 0, t_start + epochs_per_stream > 2^31 - 1, a NULL d_carry, carry_bytes
+ * or the workspace too small, a misaligned pointer (16 bytes for the record arrays and d_carry).  n_epochs = 0 succeeds and launches
+ * nothing. */
+CRN_API int crn_tracks_carry_device(crn_handle *h, const crn_segment_epoch *d_epochs, const crn_segment *d_segments, int64_t n_epochs,
+                                    const crn_track_params *params, int64_t t_start, int32_t flush, void *d_carry, int64_t carry_bytes,
+                                    crn_track_carry_stream *d_streams, crn_track *d_tracks, crn_track *d_open, void *d_workspace,
+                                    int64_t workspace_bytes, void *stream);
+
 /* Allocate, now, the device scratch and pinned staging that crn_sense_run_host needs for up to
  * max_epochs dense epochs of full-length frames (and their per-bin spectra when want_spectrum != 0),
  * and load the kernels: a later crn_sense_run_host within that size allocates nothing.  An engine

@@ -47,6 +47,7 @@ EXPORTS = [
     "crn_sense_set_cfar", "crn_sense_get_cfar", "crn_sense_run_device_cfar", "crn_cfar_alpha",
     "crn_sense_set_cfar_ex", "crn_sense_get_cfar_ex", "crn_cfar_alpha_ex",
     "crn_segments_device", "crn_tracks_workspace_bytes", "crn_tracks_device",
+    "crn_tracks_carry_bytes", "crn_tracks_carry_workspace_bytes", "crn_tracks_carry_device",
     "crn_comm_unique_id", "crn_comm_create", "crn_comm_local", "crn_comm_allgather", "crn_comm_gathered",
     "crn_comm_finish", "crn_comm_destroy", "crn_comm_local_addr", "crn_comm_wait", "crn_comm_info",
     "crn_last_error", "crn_abi_version", "crn_build_info",
@@ -125,6 +126,10 @@ TRACK_DTYPE = [("first_t", "<i4"), ("last_t", "<i4"), ("first_slot", "<i4"), ("l
                ("flags", "<i4"), ("reserved", "<i4", (2,))]
 TRACK_STREAM_DTYPE = [("n_found", "<i4"), ("n_stored", "<i4"), ("n_nodes", "<i4"), ("reserved", "<i4")]
 TRACK_BEGAN_BEFORE, TRACK_GOES_ON = 1, 2      # crn_track.flags
+TRACK_HITS_UPPER_BOUND = 4                    # crn_track.flags from crn_tracks_carry_device: two carried tracks merged, n_epochs_hit is an upper bound
+# the per-stream header crn_tracks_carry_device writes: (.., TRACK_CARRY_STREAM_DTYPE) [n_streams]
+TRACK_CARRY_STREAM_DTYPE = [("n_found", "<i4"), ("n_stored", "<i4"), ("n_nodes", "<i4"), ("n_open", "<i4"), ("n_open_found", "<i4"),
+                            ("n_open_stored", "<i4"), ("status", "<i4"), ("reserved", "<i4")]
 CFAR_METHODS = {"ca": CFAR_CA, "go": CFAR_GO, "so": CFAR_SO, "os": CFAR_OS}
 
 
@@ -245,6 +250,10 @@ def lib():
         L.crn_tracks_workspace_bytes.restype = C.c_int64
         L.crn_tracks_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(TrackParams), C.c_void_p, C.c_void_p, C.c_void_p,
                                         C.c_void_p, C.c_int64, C.c_void_p]
+        for f in (L.crn_tracks_carry_bytes, L.crn_tracks_carry_workspace_bytes):
+            f.argtypes, f.restype = [C.c_int64, C.POINTER(TrackParams)], C.c_int64
+        L.crn_tracks_carry_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(TrackParams), C.c_int64, C.c_int32, C.c_void_p,
+                                              C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
         L.crn_ingest_create.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]
         L.crn_ingest_push.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
         L.crn_ingest_flush.argtypes = [C.c_void_p]
@@ -382,6 +391,24 @@ def tracks_workspace_bytes(n_epochs, max_segments=16, epochs_per_stream=None, ma
     nb = lib().crn_tracks_workspace_bytes(int(n_epochs), C.byref(q))
     if nb <= 0:
         raise CrnError(f"crn_tracks_workspace_bytes: arguments out of range ({nb})")
+    return nb
+
+
+def tracks_carry_bytes(n_streams, max_segments=16, max_miss=0):
+    """Bytes of the per-stream carry Sensor.tracks_carry_device reads and rewrites (crn_tracks_carry_bytes): no handle, no device."""
+    q = track_params(max_segments, 1, 0, max_miss, 1, 1)
+    nb = lib().crn_tracks_carry_bytes(int(n_streams), C.byref(q))
+    if nb <= 0:
+        raise CrnError(f"crn_tracks_carry_bytes: arguments out of range ({nb})")
+    return nb
+
+
+def tracks_carry_workspace_bytes(n_epochs, max_segments=16, epochs_per_stream=None, max_miss=0):
+    """Bytes of device scratch Sensor.tracks_carry_device needs (crn_tracks_carry_workspace_bytes): no handle, no device."""
+    q = track_params(max_segments, n_epochs if epochs_per_stream is None else epochs_per_stream, 0, max_miss, 1, 1)
+    nb = lib().crn_tracks_carry_workspace_bytes(int(n_epochs), C.byref(q))
+    if nb <= 0:
+        raise CrnError(f"crn_tracks_carry_workspace_bytes: arguments out of range ({nb})")
     return nb
 
 
@@ -594,6 +621,21 @@ class Sensor:
                                       C.c_void_p(streams_ptr or None), C.c_void_p(tracks_ptr or None), C.c_void_p(track_of_ptr or None),
                                       C.c_void_p(workspace_ptr or None), int(workspace_bytes), C.c_void_p(stream or None)),
               "crn_tracks_device")
+
+    def tracks_carry_device(self, epochs_ptr, segments_ptr, n_epochs, t_start, carry_ptr, carry_bytes, streams_ptr, tracks_ptr, workspace_ptr,
+                            workspace_bytes, open_ptr=0, flush=False, max_segments=16, epochs_per_stream=None, slack_bins=1, max_miss=0,
+                            min_epochs=1, max_tracks=64, stream=0):
+        """One call of a sequence that carries tracks across batches (device pointers): the epochs t_start .. t_start + epochs_per_stream - 1
+        of every stream; t_start = 0 starts afresh.  carry_ptr: at least tracks_carry_bytes(n_streams, ...) that the caller keeps between
+        calls; streams_ptr [n_streams] TRACK_CARRY_STREAM_DTYPE; tracks_ptr [n_streams][max_tracks] TRACK_DTYPE, the records this call
+        closed; open_ptr the same shape or 0, the tracks still open; workspace_ptr at least tracks_carry_workspace_bytes(...) of scratch;
+        flush closes everything.  Only enqueues."""
+        q = track_params(max_segments, n_epochs if epochs_per_stream is None else epochs_per_stream, slack_bins, max_miss, min_epochs, max_tracks)
+        v = lambda ptr: C.c_void_p(ptr or None)      # noqa: E731
+        check(lib().crn_tracks_carry_device(self._h, v(epochs_ptr), v(segments_ptr), n_epochs, C.byref(q), int(t_start), int(bool(flush)),
+                                            v(carry_ptr), carry_bytes, v(streams_ptr), v(tracks_ptr), v(open_ptr), v(workspace_ptr),
+                                            workspace_bytes, v(stream)),
+              "crn_tracks_carry_device")
 
     def set_wire_full_scale(self, full_scale):
         _need_sc16("set_wire_full_scale")
