@@ -6,11 +6,8 @@
 // (parent [nodes] int32, one 64-byte accumulator per node, two int32 per epoch):
 //   1. init      parent[i] = i and a cleared accumulator for every stored node, -1 for the empty slots;
 //   2. link      a wave per epoch e: its segments (lo, width) in LDS, then for each d = 1 .. max_miss + 1 the stored segments of epoch
-//                e + d in LDS; lane a walks them (a broadcast read each) and unites on every hit.  The union is lock-free: find with path
-//                halving, then atomicCAS hooks the larger root under the smaller, so a parent never exceeds its child, no cycle can
-//                form, and the root of a finished component is its smallest index.  A failed CAS returns the value that beat it and the
-//                loop goes on from there; a stale read of parent[] can only show a former ancestor, which is harmless for the same reason.
-//                The lane keeps the root it reached, so the second and later unions of one segment start at the root;
+//                e + d in LDS; lane a walks them (a broadcast read each) and unites on every hit.  The union is lock-free and leaves the
+//                smallest index of a component as its root: crn_track_link.h has it, with the argument why it is safe;
 //   3. gather    a wave per epoch: every node is flattened to its root (parent[i] = root, written with atomicMin like this pass's
 //                halving, so that a slower lane's halving of the same node cannot put an older ancestor back) and adds itself to the root's accumulator
 //                (integer atomics: exact in any order; the two fp64 sums with fp64 atomic adds).  One node per (epoch, root), settled
@@ -24,18 +21,11 @@
 // A chain as long as the stream (one solid segment in every epoch) stays short under the halving; the most links (256 alternating
 // one-bin segments, max_miss 3, a wide slack) cost finds that end after one or two steps because of the kept root.
 // No scratch memory, 4 KiB of LDS at most; every write to memory is a vector store or a vector atomic.
-#include <hip/hip_runtime.h>
-
-#include <cstdint>
-#include <string>
-
-#include "crn_internal.h"
 #include "crn_segments.h"
+#include "crn_track_link.h"
 
 namespace crn {
 namespace {
-
-constexpr int MAX_SLOTS = 256;   // max_segments at most
 
 // what a root gathers from its members; 64 bytes, indexed like parent[]
 struct TrackAcc {
@@ -64,45 +54,6 @@ struct TrkParams {
 __device__ __forceinline__ int stored(const TrkParams &p, long long e) {
   const int ns = p.epochs[e].n_stored;
   return ns < 0 ? 0 : ns > p.S ? p.S : ns;
-}
-
-__device__ __forceinline__ int ld(const int *q) { return __hip_atomic_load(q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ void st(int *q, int v) { __hip_atomic_store(q, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-// the root of x as far as this lane can see, halving the path on the way (every value written is an ancestor of the node it is written
-// to).  LOWER: the halving writes are atomicMin, so a node that has been given its root keeps it whatever a slower lane writes later;
-// that is what leaves parent[] flat after the gather pass.  The link pass, where roots still move, halves with plain stores.
-template <bool LOWER>
-__device__ __forceinline__ int find(int *parent, int x) {
-  int px = ld(parent + x);
-  while (px != x) {
-    const int gp = ld(parent + px);
-    if (gp != px) {
-      if (LOWER) atomicMin(parent + x, gp);
-      else st(parent + x, gp);
-    }
-    x = px;
-    px = gp;
-  }
-  return x;
-}
-
-// unites the components of root-or-member rx and node y; returns the smaller root
-__device__ __forceinline__ int unite(int *parent, int rx, int y) {
-  rx = find<false>(parent, rx);
-  int ry = find<false>(parent, y);
-  while (rx != ry) {
-    if (rx > ry) {
-      const int t = rx;
-      rx = ry;
-      ry = t;
-    }
-    const int old = atomicCAS(parent + ry, ry, rx);
-    if (old == ry) break;
-    ry = find<false>(parent, old);   // somebody hooked ry first: go on from where it hangs now
-    rx = find<false>(parent, rx);
-  }
-  return rx < ry ? rx : ry;
 }
 
 __global__ __launch_bounds__(256) void tracks_init_kernel(const TrkParams p) {
@@ -151,15 +102,7 @@ __global__ __launch_bounds__(64) void tracks_link_kernel(const TrkParams p) {
       next[s] = make_int2(g->lo, g->width);
     }
     __syncthreads();
-    for (int a = l; a < na; a += 64) {
-      const int2 sa = mine[a];
-      int root = (int)(e * p.S) + a;
-      const int b0 = (int)((e + d) * p.S);
-      for (int b = 0; b < nb; b++) {
-        const int2 sb = next[b];
-        if (((sb.x - sa.x) & mask) < sa.y + p.slack || ((sa.x - sb.x) & mask) < sb.y + p.slack) root = unite(p.parent, root, b0 + b);
-      }
-    }
+    link_rows(p.parent, mine, na, (int)(e * p.S), next, nb, (int)((e + d) * p.S), l, mask, p.slack);
   }
 }
 
@@ -180,19 +123,10 @@ __global__ __launch_bounds__(64) void tracks_gather_kernel(const TrkParams p) {
   for (int s = l; s < ns; s += 64) {
     const int r = roots[s];
     const crn_segment g = p.segments[e * p.S + s];
-    const int off = ((g.lo - p.segments[r].lo + half) & mask) - half;
-    TrackAcc *a = p.acc + r;
+    const int off = wrapped(g.lo, p.segments[r].lo, half, mask);
     bool first = true;   // of this epoch's members of r
     for (int j = 0; j < s; j++) first = first && roots[j] != r;
-    if (first) atomicAdd(&a->hits, 1);
-    atomicAdd(&a->nseg, 1);
-    atomicMax(&a->last_key, (int)((long long)t * p.S + (p.S - 1 - s)));
-    atomicMin(&a->lo_off, off);
-    atomicMax(&a->hi_off, off + g.width - 1);
-    atomicMax(&a->peak, __float_as_uint(g.peak_power));
-    atomicAdd(&a->width_sum, (unsigned long long)g.width);
-    atomicAdd(&a->power, (double)g.power);
-    atomicAdd(&a->moment, (double)g.power * ((double)off + (double)g.centroid));
+    add_member(p.acc + r, g, off, first, t, s, p.S);
   }
 }
 
@@ -222,12 +156,7 @@ __global__ __launch_bounds__(1024) void tracks_scan_kernel(const TrkParams p) {
     sum += p.count[e0 + t];
     nodes += stored(p, e0 + t);
   }
-  int incl = sum;
-#pragma unroll
-  for (int s = 1; s < 64; s *= 2) {
-    const int y = __shfl_up(incl, s, 64);
-    if (l >= s) incl += y;
-  }
+  const int incl = wave_scan(sum, l);
 #pragma unroll
   for (int s = 32; s > 0; s /= 2) nodes += __shfl_xor(nodes, s, 64);
   if (l == 63) wave_sum[w] = incl;
@@ -254,9 +183,7 @@ __global__ __launch_bounds__(1024) void tracks_scan_kernel(const TrkParams p) {
     h.reserved = 0;
     p.streams[blockIdx.x] = h;
   }
-  // zeros in the slots beyond n_stored: 64 bytes per slot as four 16-byte stores
-  uint4 *z = reinterpret_cast<uint4 *>(p.tracks + (long long)blockIdx.x * p.max_tracks);
-  for (int k = 4 * n_stored + i; k < 4 * p.max_tracks; k += 1024) z[k] = make_uint4(0, 0, 0, 0);
+  zero_unused(p.tracks + (long long)blockIdx.x * p.max_tracks, n_stored, p.max_tracks, i);
 }
 
 __global__ __launch_bounds__(64) void tracks_emit_kernel(const TrkParams p) {
@@ -289,10 +216,7 @@ __global__ __launch_bounds__(64) void tracks_emit_kernel(const TrkParams p) {
         o.width_sum = (int64_t)v.width_sum;
         o.power_sum = (float)v.power;
         o.peak_power = __uint_as_float(v.peak);
-        double c = (double)p.segments[i].lo + (v.power > 0.0 ? v.moment / v.power : 0.0);
-        c -= (double)p.n * floor(c / (double)p.n);
-        const float cf = (float)c;
-        o.centre = cf >= (float)p.n ? 0.0f : cf;
+        o.centre = centre(p.segments[i].lo, v.moment, v.power, p.n);
         o.flags = (t <= p.max_miss ? 1 : 0) | (o.last_t >= p.eps - 1 - p.max_miss ? 2 : 0);
         o.reserved[0] = o.reserved[1] = 0;
         p.tracks[stream * p.max_tracks + k] = o;
@@ -309,16 +233,14 @@ __global__ __launch_bounds__(256) void tracks_labels_kernel(const TrkParams p) {
   p.track_of[i] = r < 0 ? -1 : p.acc[r].number;
 }
 
-// bytes of the three parts of the workspace, each a multiple of 64
+// bytes of the three parts of the workspace, each a multiple of 64; false: more than 2^31 - 1 nodes
 struct Layout {
   int64_t parent, acc, counts;
+  int64_t total() const { return 64 + parent + acc + counts; }
 };
-bool layout(int64_t n_epochs, const crn_track_params *q, Layout *out) {
-  if (!q || n_epochs < 0 || q->max_segments < 1 || q->max_segments > MAX_SLOTS || q->epochs_per_stream < 1 || n_epochs % q->epochs_per_stream != 0 ||
-      q->slack_bins < 0 || q->max_miss < 0 || q->max_miss > 15 || q->min_epochs < 1 || q->max_tracks < 1 || q->max_tracks > 1024 ||
-      q->reserved[0] != 0 || q->reserved[1] != 0 || n_epochs > INT32_MAX / q->max_segments)
-    return false;
-  const int64_t nodes = n_epochs * q->max_segments;
+bool layout(int64_t n_epochs, const crn_track_params &q, Layout *out) {
+  if (n_epochs > INT32_MAX / q.max_segments) return false;
+  const int64_t nodes = n_epochs * q.max_segments;
   out->parent = (4 * nodes + 63) / 64 * 64;
   out->acc = 64 * nodes;
   out->counts = (8 * n_epochs + 63) / 64 * 64;
@@ -330,40 +252,33 @@ bool layout(int64_t n_epochs, const crn_track_params *q, Layout *out) {
 
 int64_t crn_tracks_workspace_bytes(int64_t n_epochs, const crn_track_params *params) {
   crn::Layout w;
-  if (!crn::layout(n_epochs, params, &w)) return -1;
-  return 64 + w.parent + w.acc + w.counts;
+  if (!params || crn::track_params_refusal(*params, n_epochs) || !crn::layout(n_epochs, *params, &w)) return -1;
+  return w.total();
 }
 
 int crn_tracks_device(crn_handle *h, const crn_segment_epoch *d_epochs, const crn_segment *d_segments, int64_t n_epochs,
                       const crn_track_params *params, crn_track_stream *d_streams, crn_track *d_tracks, int32_t *d_track_of,
                       void *d_workspace, int64_t workspace_bytes, void *stream) {
   static_assert(sizeof(crn_track_params) == 32 && sizeof(crn_track) == 64 && sizeof(crn_track_stream) == 16, "include/crn_sense.h");
+  using crn::misaligned;
+  const char *who = "crn_tracks_device";
   if (!h || !params || !d_epochs || !d_segments || !d_streams || !d_tracks || !d_workspace)
-    return crn::fail(CRN_ERR_ARG, "crn_tracks_device: null handle / params / epochs / segments / streams / tracks / workspace");
-  if (n_epochs < 0) return crn::fail(CRN_ERR_ARG, "crn_tracks_device: n_epochs < 0");
+    return crn::refuse(who, "null handle / params / epochs / segments / streams / tracks / workspace");
   int n = 0, device = 0;
   crn::handle_geometry(h, &n, &device);
   const crn_track_params &q = *params;
-  if (q.max_segments < 1 || q.max_segments > 256) return crn::fail(CRN_ERR_ARG, "crn_tracks_device: max_segments must be in 1..256");
-  if (q.epochs_per_stream < 1 || n_epochs % q.epochs_per_stream != 0)
-    return crn::fail(CRN_ERR_ARG, "crn_tracks_device: epochs_per_stream must be >= 1 and divide n_epochs");
-  if (q.slack_bins < 0 || q.slack_bins >= n) return crn::fail(CRN_ERR_ARG, "crn_tracks_device: slack_bins must be in 0..fft_len - 1");
-  if (q.max_miss < 0 || q.max_miss > 15) return crn::fail(CRN_ERR_ARG, "crn_tracks_device: max_miss must be in 0..15");
-  if (q.min_epochs < 1) return crn::fail(CRN_ERR_ARG, "crn_tracks_device: min_epochs < 1");
-  if (q.max_tracks < 1 || q.max_tracks > 1024) return crn::fail(CRN_ERR_ARG, "crn_tracks_device: max_tracks must be in 1..1024");
-  if (q.reserved[0] != 0 || q.reserved[1] != 0) return crn::fail(CRN_ERR_ARG, "crn_tracks_device: reserved must be 0");
+  if (const char *why = crn::track_params_refusal(q, n_epochs, n)) return crn::refuse(who, why);
   crn::Layout w;
-  if (!crn::layout(n_epochs, params, &w)) return crn::fail(CRN_ERR_ARG, "crn_tracks_device: n_epochs x max_segments must stay below 2^31");
-  auto mis = [](const void *ptr, uintptr_t a) { return (reinterpret_cast<uintptr_t>(ptr) & (a - 1)) != 0; };
-  if (mis(d_epochs, 16) || mis(d_segments, 16) || mis(d_streams, 16) || mis(d_tracks, 16) || mis(d_track_of, 4) || mis(d_workspace, 8))
-    return crn::fail(CRN_ERR_ARG, "crn_tracks_device: d_epochs, d_segments, d_streams and d_tracks must be 16-byte, d_workspace 8-byte, d_track_of 4-byte aligned");
-  if (workspace_bytes < 64 + w.parent + w.acc + w.counts)
-    return crn::fail(CRN_ERR_ARG, "crn_tracks_device: workspace smaller than crn_tracks_workspace_bytes");
+  if (!crn::layout(n_epochs, q, &w)) return crn::refuse(who, "n_epochs x max_segments must stay below 2^31");
+  if (misaligned(d_epochs, 16) || misaligned(d_segments, 16) || misaligned(d_streams, 16) || misaligned(d_tracks, 16) || misaligned(d_track_of, 4) ||
+      misaligned(d_workspace, 8))
+    return crn::refuse(who, "d_epochs, d_segments, d_streams and d_tracks must be 16-byte, d_workspace 8-byte, d_track_of 4-byte aligned");
+  if (workspace_bytes < w.total()) return crn::refuse(who, "workspace smaller than crn_tracks_workspace_bytes");
   if (n_epochs == 0) return CRN_OK;
   hipError_t err = hipSetDevice(device);
-  if (err != hipSuccess) return crn::fail(CRN_ERR_DEVICE, std::string("crn_tracks_device: ") + hipGetErrorString(err));
+  if (err != hipSuccess) return crn::fail_hip(who, err);
   hipStream_t st = static_cast<hipStream_t>(stream);
-  char *ws = reinterpret_cast<char *>((reinterpret_cast<uintptr_t>(d_workspace) + 63) & ~uintptr_t(63));
+  char *ws = crn::align64(d_workspace);
   crn::TrkParams p;
   p.epochs = d_epochs;
   p.segments = d_segments;
@@ -392,6 +307,6 @@ int crn_tracks_device(crn_handle *h, const crn_segment_epoch *d_epochs, const cr
   hipLaunchKernelGGL(crn::tracks_emit_kernel, dim3(per_epoch), dim3(64), 0, st, p);
   if (d_track_of) hipLaunchKernelGGL(crn::tracks_labels_kernel, dim3(per_slot), dim3(256), 0, st, p);
   err = hipGetLastError();
-  if (err != hipSuccess) return crn::fail(CRN_ERR_DEVICE, std::string("crn_tracks_device: ") + hipGetErrorString(err));
+  if (err != hipSuccess) return crn::fail_hip(who, err);
   return CRN_OK;
 }

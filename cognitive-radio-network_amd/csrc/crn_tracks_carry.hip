@@ -9,7 +9,7 @@
 //   1. init     the old carry is read once, here: the stream's mark is checked (a carry that does not match is an empty one); a ghost's
 //               accumulator is the carried one, parent[tail node] = its ghost (the index clamped), a new node is its own root with an
 //               empty accumulator; the tail's (lo, width) pairs and the counts go to the workspace.  Nothing later reads the carry;
-//   2. link     a wave per tail or new row: crn_tracks.hip's link pass with the same lock-free union, partners in NEW rows only;
+//   2. link     a wave per tail or new row: crn_tracks.hip's link pass, partners in NEW rows only;
 //   3. gather   a wave per row.  New nodes add themselves to their root as in crn_tracks.hip, offsets taken from the root's lo_root;
 //               tail nodes are only flattened (they were counted by the call that stored them); a ghost that is not its root adds its
 //               accumulator re-based by delta;
@@ -17,21 +17,17 @@
 //   5. scan     a workgroup per stream: three exclusive scans over the rows, the stream's header, the zero fill, the new carry's header;
 //   6. emit     a wave per row: closed roots to d_tracks, open roots to the new carry (and d_open); each open root keeps its position;
 //   7. tail     a wave per row of the new tail: (lo, width, position of the open track) of the last H epochs up to T.
-// The union-find helpers are those of crn_tracks.hip, repeated here so that file stays instruction for instruction what it is.
+// The lock-free union, the link condition with its pair loop, a member's add, the centre, the zero fill and the wave scan are the ones
+// crn_tracks.hip uses, from crn_track_link.h; so is the rule for a usable crn_track_params.
 // No scratch memory, 4 KiB of LDS at most; every write to memory is a vector store or a vector atomic.
-#include <hip/hip_runtime.h>
-
 #include <cstddef>
-#include <cstdint>
-#include <string>
 
-#include "crn_internal.h"
 #include "crn_segments.h"
+#include "crn_track_link.h"
 
 namespace crn {
 namespace {
 
-constexpr int MAX_SLOTS = 256;   // max_segments at most
 constexpr int MAX_H = 16;        // max_miss + 1 at most
 constexpr int MAGIC = 0x43524e54;
 
@@ -103,44 +99,6 @@ __device__ __forceinline__ int2 lo_width(const CarryParams &p, int stream, int j
 }
 // node index of (row j of the tail-and-new part, slot s)
 __device__ __forceinline__ int node(const CarryParams &p, int stream, int j, int s) { return (stream * p.R + p.H + j) * p.S + s; }
-
-__device__ __forceinline__ int ld(const int *q) { return __hip_atomic_load(q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ void st(int *q, int v) { __hip_atomic_store(q, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-// crn_tracks.hip's find: the root of x as far as this lane can see, halving the path on the way.  LOWER: the halving writes are
-// atomicMin, so a node that has been given its root keeps it whatever a slower lane writes later (the gather pass).
-template <bool LOWER>
-__device__ __forceinline__ int find(int *parent, int x) {
-  int px = ld(parent + x);
-  while (px != x) {
-    const int gp = ld(parent + px);
-    if (gp != px) {
-      if (LOWER) atomicMin(parent + x, gp);
-      else st(parent + x, gp);
-    }
-    x = px;
-    px = gp;
-  }
-  return x;
-}
-
-// crn_tracks.hip's unite: one atomicCAS hooks the larger root under the smaller; returns the smaller root
-__device__ __forceinline__ int unite(int *parent, int rx, int y) {
-  rx = find<false>(parent, rx);
-  int ry = find<false>(parent, y);
-  while (rx != ry) {
-    if (rx > ry) {
-      const int t = rx;
-      rx = ry;
-      ry = t;
-    }
-    const int old = atomicCAS(parent + ry, ry, rx);
-    if (old == ry) break;
-    ry = find<false>(parent, old);
-    rx = find<false>(parent, rx);
-  }
-  return rx < ry ? rx : ry;
-}
 
 // one thread per node
 __global__ __launch_bounds__(256) void carry_init_kernel(const CarryParams p) {
@@ -228,15 +186,7 @@ __global__ __launch_bounds__(64) void carry_link_kernel(const CarryParams p) {
     __syncthreads();   // the previous round's reads of next[] are over (and mine[] is written)
     for (int s = l; s < nb; s += 64) next[s] = lo_width(p, stream, j + d, s);
     __syncthreads();
-    for (int a = l; a < na; a += 64) {
-      const int2 sa = mine[a];
-      int root = node(p, stream, j, a);
-      const int b0 = node(p, stream, j + d, 0);
-      for (int b = 0; b < nb; b++) {
-        const int2 sb = next[b];
-        if (((sb.x - sa.x) & mask) < sa.y + p.slack || ((sa.x - sb.x) & mask) < sb.y + p.slack) root = unite(p.parent, root, b0 + b);
-      }
-    }
+    link_rows(p.parent, mine, na, node(p, stream, j, 0), next, nb, node(p, stream, j + d, 0), l, mask, p.slack);
   }
 }
 
@@ -256,7 +206,7 @@ __global__ __launch_bounds__(64) void carry_gather_kernel(const CarryParams p) {
       atomicMin(p.parent + i, r);
       const CarryAcc b = p.acc[i];
       CarryAcc *a = p.acc + r;
-      const int delta = ((b.lo_root - a->lo_root + half) & mask) - half;
+      const int delta = wrapped(b.lo_root, a->lo_root, half, mask);
       atomicAdd(&a->hits, b.hits);
       atomicAdd(&a->nseg, b.nseg);
       atomicMax(&a->last_key, b.last_key);
@@ -288,18 +238,10 @@ __global__ __launch_bounds__(64) void carry_gather_kernel(const CarryParams p) {
     const int r = roots[s];
     const crn_segment g = p.segments[ge * p.S + s];
     CarryAcc *a = p.acc + r;
-    const int off = ((g.lo - a->lo_root + half) & mask) - half;
+    const int off = wrapped(g.lo, a->lo_root, half, mask);
     bool first = true;   // of this epoch's members of r
     for (int k = 0; k < s; k++) first = first && roots[k] != r;
-    if (first) atomicAdd(&a->hits, 1);
-    atomicAdd(&a->nseg, 1);
-    atomicMax(&a->last_key, (unsigned long long)(p.t_start + e) * p.S + (p.S - 1 - s));
-    atomicMin(&a->lo_off, off);
-    atomicMax(&a->hi_off, off + g.width - 1);
-    atomicMax(&a->peak, __float_as_uint(g.peak_power));
-    atomicAdd(&a->width_sum, (unsigned long long)g.width);
-    atomicAdd(&a->power, (double)g.power);
-    atomicAdd(&a->moment, (double)g.power * ((double)off + (double)g.centroid));
+    add_member(a, g, off, first, p.t_start + e, s, p.S);
   }
 }
 
@@ -369,12 +311,7 @@ __global__ __launch_bounds__(1024) void carry_scan_kernel(const CarryParams p) {
   int incl[3];
 #pragma unroll
   for (int c = 0; c < 3; c++) {
-    incl[c] = sum[c];
-#pragma unroll
-    for (int s = 1; s < 64; s *= 2) {
-      const int y = __shfl_up(incl[c], s, 64);
-      if (l >= s) incl[c] += y;
-    }
+    incl[c] = wave_scan(sum[c], l);
     if (l == 63) wave_sum[c][w] = incl[c];
   }
 #pragma unroll
@@ -426,13 +363,8 @@ __global__ __launch_bounds__(1024) void carry_scan_kernel(const CarryParams p) {
     else if (i >= 16 && i - 16 < p.H && !p.flush) v = stored(p, stream, i - 16 + p.eps);
     reinterpret_cast<int *>(carry_header(p, stream))[i] = v;
   }
-  // zeros in the slots beyond n_stored: 64 bytes per slot as four 16-byte stores
-  uint4 *z = reinterpret_cast<uint4 *>(p.tracks + (long long)stream * p.max_tracks);
-  for (int k = 4 * n_stored + i; k < 4 * p.max_tracks; k += 1024) z[k] = make_uint4(0, 0, 0, 0);
-  if (p.open) {
-    z = reinterpret_cast<uint4 *>(p.open + (long long)stream * p.max_tracks);
-    for (int k = 4 * n_open_stored + i; k < 4 * p.max_tracks; k += 1024) z[k] = make_uint4(0, 0, 0, 0);
-  }
+  zero_unused(p.tracks + (long long)stream * p.max_tracks, n_stored, p.max_tracks, i);
+  if (p.open) zero_unused(p.open + (long long)stream * p.max_tracks, n_open_stored, p.max_tracks, i);
 }
 
 __device__ __forceinline__ crn_track record(const CarryParams &p, const CarryAcc &a, const Settled &v) {
@@ -448,10 +380,7 @@ __device__ __forceinline__ crn_track record(const CarryParams &p, const CarryAcc
   o.width_sum = (int64_t)a.width_sum;
   o.power_sum = (float)a.power;
   o.peak_power = __uint_as_float(a.peak);
-  double c = (double)a.lo_root + (a.power > 0.0 ? a.moment / a.power : 0.0);
-  c -= (double)p.n * floor(c / (double)p.n);
-  const float cf = (float)c;
-  o.centre = cf >= (float)p.n ? 0.0f : cf;
+  o.centre = centre(a.lo_root, a.moment, a.power, p.n);
   o.flags = (a.root_t <= p.max_miss ? 1 : 0) | (v.last_t >= p.t_start + p.eps - 1 - p.max_miss ? 2 : 0) | (v.merged ? 4 : 0);
   o.reserved[0] = o.reserved[1] = 0;
   return o;
@@ -517,29 +446,25 @@ __global__ __launch_bounds__(64) void carry_tail_kernel(const CarryParams p) {
   }
 }
 
-// bytes of the parts of the workspace, each a multiple of 64; rows and nodes over all streams
+// bytes of the parts of the workspace, each a multiple of 64; rows and nodes over all streams; false: more than 2^31 - 1 nodes
 struct Layout {
   int64_t rows, nodes, parent, acc, state, tail, counts;
   int64_t total() const { return 64 + parent + acc + state + tail + 2 * counts; }
 };
-bool params_ok(const crn_track_params *q) {
-  return q && q->max_segments >= 1 && q->max_segments <= MAX_SLOTS && q->epochs_per_stream >= 1 && q->slack_bins >= 0 && q->max_miss >= 0 &&
-         q->max_miss < MAX_H && q->min_epochs >= 1 && q->max_tracks >= 1 && q->max_tracks <= 1024 && q->reserved[0] == 0 && q->reserved[1] == 0;
+int64_t carry_stride(const crn_track_params &q) {
+  return (int64_t)sizeof(CarryHeader) + (int64_t)(q.max_miss + 1) * q.max_segments * (16 + (int64_t)sizeof(CarryAcc));
 }
-int64_t carry_stride(const crn_track_params *q) {
-  return (int64_t)sizeof(CarryHeader) + (int64_t)(q->max_miss + 1) * q->max_segments * (16 + (int64_t)sizeof(CarryAcc));
-}
-bool layout(int64_t n_epochs, const crn_track_params *q, Layout *out) {
-  if (!params_ok(q) || n_epochs < 0 || n_epochs % q->epochs_per_stream != 0 || n_epochs > INT32_MAX / q->max_segments) return false;
-  const int64_t n_streams = n_epochs / q->epochs_per_stream, H = q->max_miss + 1;
+bool layout(int64_t n_epochs, const crn_track_params &q, Layout *out) {
+  if (n_epochs > INT32_MAX / q.max_segments) return false;
+  const int64_t n_streams = n_epochs / q.epochs_per_stream, H = q.max_miss + 1;
   out->rows = n_epochs + n_streams * 2 * H;
-  out->nodes = out->rows * q->max_segments;
+  out->nodes = out->rows * q.max_segments;
   if (out->nodes > INT32_MAX) return false;
   out->parent = (4 * out->nodes + 63) / 64 * 64;
   out->acc = (int64_t)sizeof(CarryAcc) * out->nodes;
   out->acc = (out->acc + 63) / 64 * 64;
   out->state = (int64_t)sizeof(StreamState) * n_streams;
-  out->tail = (8 * n_streams * H * q->max_segments + 63) / 64 * 64;
+  out->tail = (8 * n_streams * H * q.max_segments + 63) / 64 * 64;
   out->counts = (12 * out->rows + 63) / 64 * 64;
   return true;
 }
@@ -548,13 +473,13 @@ bool layout(int64_t n_epochs, const crn_track_params *q, Layout *out) {
 }  // namespace crn
 
 int64_t crn_tracks_carry_bytes(int64_t n_streams, const crn_track_params *params) {
-  if (!crn::params_ok(params) || n_streams < 0 || n_streams > INT32_MAX) return -1;
-  return n_streams > 0 ? n_streams * crn::carry_stride(params) : 16;   // positive for valid arguments, like the workspace sizes
+  if (!params || crn::track_params_refusal(*params, 0) || n_streams < 0 || n_streams > INT32_MAX) return -1;
+  return n_streams > 0 ? n_streams * crn::carry_stride(*params) : 16;   // positive for valid arguments, like the workspace sizes
 }
 
 int64_t crn_tracks_carry_workspace_bytes(int64_t n_epochs, const crn_track_params *params) {
   crn::Layout w;
-  if (!crn::layout(n_epochs, params, &w)) return -1;
+  if (!params || crn::track_params_refusal(*params, n_epochs) || !crn::layout(n_epochs, *params, &w)) return -1;
   return w.total();
 }
 
@@ -563,36 +488,29 @@ int crn_tracks_carry_device(crn_handle *h, const crn_segment_epoch *d_epochs, co
                             crn_track_carry_stream *d_streams, crn_track *d_tracks, crn_track *d_open, void *d_workspace,
                             int64_t workspace_bytes, void *stream) {
   static_assert(sizeof(crn_track_carry_stream) == 32, "include/crn_sense.h");
+  using crn::misaligned;
+  const char *who = "crn_tracks_carry_device";
   if (!h || !params || !d_epochs || !d_segments || !d_carry || !d_streams || !d_tracks || !d_workspace)
-    return crn::fail(CRN_ERR_ARG, "crn_tracks_carry_device: null handle / params / epochs / segments / carry / streams / tracks / workspace");
-  if (n_epochs < 0) return crn::fail(CRN_ERR_ARG, "crn_tracks_carry_device: n_epochs < 0");
+    return crn::refuse(who, "null handle / params / epochs / segments / carry / streams / tracks / workspace");
   int n = 0, device = 0;
   crn::handle_geometry(h, &n, &device);
   const crn_track_params &q = *params;
-  if (q.max_segments < 1 || q.max_segments > 256) return crn::fail(CRN_ERR_ARG, "crn_tracks_carry_device: max_segments must be in 1..256");
-  if (q.epochs_per_stream < 1 || n_epochs % q.epochs_per_stream != 0)
-    return crn::fail(CRN_ERR_ARG, "crn_tracks_carry_device: epochs_per_stream must be >= 1 and divide n_epochs");
-  if (q.slack_bins < 0 || q.slack_bins >= n) return crn::fail(CRN_ERR_ARG, "crn_tracks_carry_device: slack_bins must be in 0..fft_len - 1");
-  if (q.max_miss < 0 || q.max_miss > 15) return crn::fail(CRN_ERR_ARG, "crn_tracks_carry_device: max_miss must be in 0..15");
-  if (q.min_epochs < 1) return crn::fail(CRN_ERR_ARG, "crn_tracks_carry_device: min_epochs < 1");
-  if (q.max_tracks < 1 || q.max_tracks > 1024) return crn::fail(CRN_ERR_ARG, "crn_tracks_carry_device: max_tracks must be in 1..1024");
-  if (q.reserved[0] != 0 || q.reserved[1] != 0) return crn::fail(CRN_ERR_ARG, "crn_tracks_carry_device: reserved must be 0");
+  if (const char *why = crn::track_params_refusal(q, n_epochs, n)) return crn::refuse(who, why);
   if (t_start < 0 || t_start + q.epochs_per_stream > INT32_MAX)
-    return crn::fail(CRN_ERR_ARG, "crn_tracks_carry_device: t_start must be >= 0 and t_start + epochs_per_stream at most 2^31 - 1");
+    return crn::refuse(who, "t_start must be >= 0 and t_start + epochs_per_stream at most 2^31 - 1");
   crn::Layout w;
-  if (!crn::layout(n_epochs, params, &w))
-    return crn::fail(CRN_ERR_ARG, "crn_tracks_carry_device: (n_epochs + 2 (max_miss + 1) streams) x max_segments must stay below 2^31");
+  if (!crn::layout(n_epochs, q, &w)) return crn::refuse(who, "(n_epochs + 2 (max_miss + 1) streams) x max_segments must stay below 2^31");
   const int64_t n_streams = n_epochs / q.epochs_per_stream;
-  auto mis = [](const void *ptr, uintptr_t a) { return (reinterpret_cast<uintptr_t>(ptr) & (a - 1)) != 0; };
-  if (mis(d_epochs, 16) || mis(d_segments, 16) || mis(d_streams, 16) || mis(d_tracks, 16) || mis(d_open, 16) || mis(d_carry, 16) || mis(d_workspace, 8))
-    return crn::fail(CRN_ERR_ARG, "crn_tracks_carry_device: d_epochs, d_segments, d_streams, d_tracks, d_open and d_carry must be 16-byte, d_workspace 8-byte aligned");
-  if (carry_bytes < crn_tracks_carry_bytes(n_streams, params)) return crn::fail(CRN_ERR_ARG, "crn_tracks_carry_device: carry smaller than crn_tracks_carry_bytes");
-  if (workspace_bytes < w.total()) return crn::fail(CRN_ERR_ARG, "crn_tracks_carry_device: workspace smaller than crn_tracks_carry_workspace_bytes");
+  if (misaligned(d_epochs, 16) || misaligned(d_segments, 16) || misaligned(d_streams, 16) || misaligned(d_tracks, 16) || misaligned(d_open, 16) ||
+      misaligned(d_carry, 16) || misaligned(d_workspace, 8))
+    return crn::refuse(who, "d_epochs, d_segments, d_streams, d_tracks, d_open and d_carry must be 16-byte, d_workspace 8-byte aligned");
+  if (carry_bytes < crn_tracks_carry_bytes(n_streams, params)) return crn::refuse(who, "carry smaller than crn_tracks_carry_bytes");
+  if (workspace_bytes < w.total()) return crn::refuse(who, "workspace smaller than crn_tracks_carry_workspace_bytes");
   if (n_epochs == 0) return CRN_OK;
   hipError_t err = hipSetDevice(device);
-  if (err != hipSuccess) return crn::fail(CRN_ERR_DEVICE, std::string("crn_tracks_carry_device: ") + hipGetErrorString(err));
+  if (err != hipSuccess) return crn::fail_hip(who, err);
   hipStream_t st = static_cast<hipStream_t>(stream);
-  char *ws = reinterpret_cast<char *>((reinterpret_cast<uintptr_t>(d_workspace) + 63) & ~uintptr_t(63));
+  char *ws = crn::align64(d_workspace);
   crn::CarryParams p;
   p.epochs = d_epochs;
   p.segments = d_segments;
@@ -606,7 +524,7 @@ int crn_tracks_carry_device(crn_handle *h, const crn_segment_epoch *d_epochs, co
   p.tail_lw = reinterpret_cast<int2 *>(ws + w.parent + w.acc + w.state);
   p.count = reinterpret_cast<int *>(ws + w.parent + w.acc + w.state + w.tail);
   p.base = reinterpret_cast<int *>(ws + w.parent + w.acc + w.state + w.tail + w.counts);
-  p.carry_stride = crn::carry_stride(params);
+  p.carry_stride = crn::carry_stride(q);
   p.n_streams = (int)n_streams;
   p.n = n;
   p.S = q.max_segments;
@@ -629,6 +547,6 @@ int crn_tracks_carry_device(crn_handle *h, const crn_segment_epoch *d_epochs, co
   hipLaunchKernelGGL(crn::carry_emit_kernel, dim3(per_row), dim3(64), 0, st, p);
   if (!p.flush) hipLaunchKernelGGL(crn::carry_tail_kernel, dim3(per_tail_row), dim3(64), 0, st, p);
   err = hipGetLastError();
-  if (err != hipSuccess) return crn::fail(CRN_ERR_DEVICE, std::string("crn_tracks_carry_device: ") + hipGetErrorString(err));
+  if (err != hipSuccess) return crn::fail_hip(who, err);
   return CRN_OK;
 }

@@ -3,38 +3,15 @@ scratch.  `make asm` writes the resource remarks of the sensing kernels only, so
 with the library's flags and -Rpass-analysis=kernel-resource-usage (the same parse as tests/test_cfar_resources.py)."""
 import os
 import re
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "cognitive-radio-network_amd", "csrc")
-HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+from hip_resources import CSRC, compile_unit, kernels as _kernels
 
 
 @pytest.fixture(scope="module")
 def remarks(tmp_path_factory):
-    out = tmp_path_factory.mktemp("segments") / "crn_segments.o"
-    mk = open(os.path.join(CSRC, "Makefile")).read()
-    flags = re.search(r"^FLAGS\s*:=\s*(.*?)\n(?=#)", mk, re.S | re.M).group(1).replace("\\\n", " ").replace("$(ARCH)", "gfx950").split()
-    r = subprocess.run([HIPCC, *flags, "--cuda-device-only", "-Wno-unused-command-line-argument", "-Rpass-analysis=kernel-resource-usage",
-                        "-c", "-o", str(out), os.path.join(CSRC, "crn_segments.hip")], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
-    return r.stderr
-
-
-def _kernels(txt):
-    out = {}
-    for b in re.split(r"remark: [^\n]*Function Name: ", txt)[1:]:
-        name = b.split('\n')[0].strip().split(' ')[0]
-
-        def g(k):
-            m = re.search(k + r": (\d+)", b)
-            return int(m.group(1)) if m else None
-        dem = subprocess.run(['c++filt', name], capture_output=True, text=True).stdout.strip()
-        out[dem] = {"scratch": g(r"ScratchSize \[bytes/lane\]"), "occ": g(r"Occupancy \[waves/SIMD\]"), "vgprs": g(r" VGPRs"),
-                    "lds": g(r"LDS Size \[bytes/block\]")}
-    return out
+    return compile_unit(tmp_path_factory, "crn_segments")[0]
 
 
 def test_segment_kernels_do_not_spill(remarks):

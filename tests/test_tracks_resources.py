@@ -5,13 +5,10 @@ that the union hooks with one vector compare-and-swap, that the fp64 sums are na
 and that nothing but vector instructions writes memory."""
 import os
 import re
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "cognitive-radio-network_amd", "csrc")
-HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+from hip_resources import CSRC, compile_unit, kernels
 
 # LDS bytes per workgroup: link holds two lists of 256 (lo, width) pairs, gather the 256 roots of its epoch, scan two words per wave
 LDS = {"tracks_init_kernel": 0, "tracks_link_kernel": 4096, "tracks_gather_kernel": 1024, "tracks_count_kernel": 0,
@@ -20,28 +17,11 @@ LDS = {"tracks_init_kernel": 0, "tracks_link_kernel": 4096, "tracks_gather_kerne
 
 @pytest.fixture(scope="module")
 def compiled(tmp_path_factory):
-    out = tmp_path_factory.mktemp("tracks") / "crn_tracks.s"
-    mk = open(os.path.join(CSRC, "Makefile")).read()
-    flags = re.search(r"^FLAGS\s*:=\s*(.*?)\n(?=#)", mk, re.S | re.M).group(1).replace("\\\n", " ").replace("$(ARCH)", "gfx950").split()
-    r = subprocess.run([HIPCC, *flags, "--cuda-device-only", "-Wno-unused-command-line-argument", "-Rpass-analysis=kernel-resource-usage",
-                        "-S", "-o", str(out), os.path.join(CSRC, "crn_tracks.hip")], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
-    return r.stderr, open(out).read()
+    return compile_unit(tmp_path_factory, "crn_tracks")
 
 
 def _kernels(txt):
-    out = {}
-    for b in re.split(r"remark: [^\n]*Function Name: ", txt)[1:]:
-        name = b.split('\n')[0].strip().split(' ')[0]
-
-        def g(k):
-            m = re.search(k + r": (\d+)", b)
-            return int(m.group(1)) if m else None
-        dem = subprocess.run(['c++filt', name], capture_output=True, text=True).stdout.strip()
-        short = re.search(r"(tracks_\w+_kernel)", dem)
-        out[short.group(1) if short else dem] = {"scratch": g(r"ScratchSize \[bytes/lane\]"), "occ": g(r"Occupancy \[waves/SIMD\]"),
-                                                 "vgprs": g(r" VGPRs"), "lds": g(r"LDS Size \[bytes/block\]")}
-    return out
+    return kernels(txt, r"(tracks_\w+_kernel)")
 
 
 def test_track_kernels_do_not_spill(compiled):

@@ -47,20 +47,7 @@ def _one_stream(state, n_stored, segs, n, t_start, flush, slack_bins, max_miss, 
     rows = [[(g[0], g[1]) for g in state["tail"][j]] for j in range(H)]
     rows += [[(int(lo[e, s]), int(width[e, s])) for s in range(int(n_stored[e]))] for e in range(eps)]
     base = np.concatenate(([G], G + np.cumsum([len(r) for r in rows]))).astype(np.int64)      # first node of each row
-    parent = list(range(int(base[-1])))
-
-    def find(x):
-        r = x
-        while parent[r] != r:
-            r = parent[r]
-        while parent[x] != r:
-            parent[x], x = r, parent[x]
-        return r
-
-    def union(a, b):
-        ra, rb = find(a), find(b)
-        if ra != rb:
-            parent[max(ra, rb)] = min(ra, rb)
+    find, union = tk.union_find(int(base[-1]))
     for j in range(H):
         for s, g in enumerate(state["tail"][j]):
             union(int(base[j]) + s, g[2])

@@ -28,10 +28,9 @@ def linked(lo_a, w_a, lo_b, w_b, n, slack_bins):
     return ((lo_b - lo_a) % n < w_a + slack_bins) | ((lo_a - lo_b) % n < w_b + slack_bins)
 
 
-def components(n_stored, lo, width, n, epochs_per_stream, slack_bins, max_miss):
-    """Steps 1-3: root[E][S], the root's node index for every stored node and -1 for the empty slots."""
-    E, S = lo.shape
-    parent = list(range(E * S))
+def union_find(n_nodes):
+    """(find, union) over the nodes 0 .. n_nodes - 1, each its own component at first; the root of a component is its smallest node."""
+    parent = list(range(n_nodes))
 
     def find(x):
         r = x
@@ -40,6 +39,18 @@ def components(n_stored, lo, width, n, epochs_per_stream, slack_bins, max_miss):
         while parent[x] != r:
             parent[x], x = r, parent[x]
         return r
+
+    def union(a, b):
+        ra, rb = find(a), find(b)
+        if ra != rb:
+            parent[max(ra, rb)] = min(ra, rb)
+    return find, union
+
+
+def components(n_stored, lo, width, n, epochs_per_stream, slack_bins, max_miss):
+    """Steps 1-3: root[E][S], the root's node index for every stored node and -1 for the empty slots."""
+    E, S = lo.shape
+    find, union = union_find(E * S)
     for d in range(1, max_miss + 2):
         for e in range(E - d):
             na, nb = int(n_stored[e]), int(n_stored[e + d])
@@ -47,9 +58,7 @@ def components(n_stored, lo, width, n, epochs_per_stream, slack_bins, max_miss):
                 continue
             hit = linked(lo[e, :na, None], width[e, :na, None], lo[e + d, None, :nb], width[e + d, None, :nb], n, slack_bins)
             for a, b in np.argwhere(hit):
-                ra, rb = find(e * S + int(a)), find((e + d) * S + int(b))
-                if ra != rb:
-                    parent[max(ra, rb)] = min(ra, rb)
+                union(e * S + int(a), (e + d) * S + int(b))
     root = np.full((E, S), -1, np.int64)
     for e in range(E):
         for s in range(int(n_stored[e])):
