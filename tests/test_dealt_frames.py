@@ -2,27 +2,27 @@
 512 / 1024 points (no window, or the periodic Hann of the Welch plans), the engine's one-epoch launch first of all (reference: one epoch of ten 512-point frames per
 sensing period, CE_Predictive_Node.cpp:148-156).  An epoch's frames are spread over the lane groups of one workgroup and the K-frame
 accumulate is replayed in frame order afterwards, so every output must be BIT FOR BIT what the streaming form gives on the same
-input: that equality is the test (the streaming form's parity with the oracle is everything else in tests/), plus the oracle directly
-on the engine's own shape."""
+input: that equality is the test, plus the oracle directly on the engine's own shape.  (The streaming forms' own parity — with float64
+and the oracle, at 512 / 1024 points over many workgroups — is tests/test_streaming_small_gpu.py, which also extends the equality
+below to batches of 50 - 100 epochs, and the three streaming-geometry tests of tests/test_gpu_parity.py; every other 512 / 1024-point
+test of at most one epoch per compute unit runs the dealt form.  Each leg names its form through tests/forms.py.)"""
 import numpy as np
 import pytest
 
 import crnsense as cs
+import forms
 import oracle_py as orc
 import signals
-
-AUTO, NEVER, ALWAYS = 400, 401, 402          # crn_sense_set_variant codes of the dealt form
 
 
 def _both(cfg, iq, n_epochs, L, want_spectrum=False, epoch_stride=0, has_dealt_form=True):
     res = []
-    for code in (NEVER, ALWAYS):
-        s = cs.Sensor(cfg)
-        s.set_variant(code)
+    assert forms.has_dealt_form(cfg, L) == has_dealt_form
+    for form in ("streaming", "dealt"):
+        s = forms.sensor(cfg, form)
         res.append(s.run_host(iq, n_epochs, L=L, want_spectrum=want_spectrum, epoch_stride=epoch_stride))
-        n_dealt = s.dealt_launches()
+        forms.assert_ran(s, form, 1, L=L)
         s.close()
-        assert (n_dealt > 0) == (code == ALWAYS and has_dealt_form), (code, n_dealt)
     return res
 
 
@@ -178,9 +178,8 @@ def test_dealt_frames_in_the_wire_format(built):
             host_f = (raw.astype(np.float32) / np.float32(32768.0)).ravel()
             d_raw, d_f = torch.from_numpy(raw.copy()).to(dev), torch.from_numpy(host_f).to(dev)
             res = {}
-            for code in (NEVER, ALWAYS):
-                s = cs.Sensor(cfg)
-                s.set_variant(code)
+            for form in ("streaming", "dealt"):
+                s = forms.sensor(cfg, form)
                 for sc in (False, True):
                     feats = torch.zeros(n, cfg.n_bands, device=dev)
                     ann = torch.zeros(n, 3, dtype=torch.float64, device=dev)
@@ -190,11 +189,11 @@ def test_dealt_frames_in_the_wire_format(built):
                                  {"features": feats.data_ptr(), "ann_out": ann.data_ptr(), "decision": dec.data_ptr(),
                                   "occupancy": occ.data_ptr(), "spectrum": 0}, sc16=sc)
                     torch.cuda.synchronize()
-                    res[code, sc] = (feats, ann, dec, occ)
-                assert s.dealt_launches() == (2 if code == ALWAYS else 0)
+                    res[form, sc] = (feats, ann, dec, occ)
+                forms.assert_ran(s, form, 2, L=L)
                 s.close()
-            for other in ((NEVER, True), (ALWAYS, False), (ALWAYS, True)):
-                for x, y in zip(res[NEVER, False], res[other]):
+            for other in (("streaming", True), ("dealt", False), ("dealt", True)):
+                for x, y in zip(res["streaming", False], res[other]):
                     assert torch.equal(x, y), other
 
 

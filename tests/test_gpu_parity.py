@@ -18,6 +18,7 @@ import numpy as np
 import pytest
 
 import crnsense as cs
+import forms
 import oracle_py as orc
 import parity_policy as pol
 import signals
@@ -1114,9 +1115,10 @@ def test_streaming_workgroups_over_several_epoch_groups(built, n, n_epochs, epw)
         cfg = cs.cfg_energy_scaled(n, 4.0)
         cfg.frames_per_epoch = K
         iq, picks = signals.make_epochs(cfg, n_epochs, seed=n + epw + K)
-        s = cs.Sensor(cfg)
+        s = forms.sensor(cfg, "streaming")      # (left to itself a launch of 67 epochs at 512 points is dealt, and epw means nothing)
         s.set_variant(100 + epw)
         got = s.run_host(iq, n_epochs, want_spectrum=(K == 3))
+        assert s.dealt_launches() == 0
         s.close()
         want = orc.run(cfg, iq, n_epochs, want_spectrum=(K == 3))
         assert np.allclose(got["features"], want["features"], rtol=1e-5, atol=0)
@@ -1133,10 +1135,11 @@ def test_graded_workgroups_cover_every_epoch_once(built, n, n_epochs, epw, tail)
     (tail capped at a quarter of the groups; none), every epoch is computed exactly once."""
     cfg = cs.cfg_energy_scaled(n, 4.0)
     iq, picks = signals.make_epochs(cfg, n_epochs, seed=7 * n + tail)
-    s = cs.Sensor(cfg)
+    s = forms.sensor(cfg, "streaming")
     s.set_variant(100 + epw)
     s.set_variant(200 + tail // 256)
     got = s.run_host(iq, n_epochs)
+    assert s.dealt_launches() == 0
     s.close()
     want = orc.run(cfg, iq, n_epochs)
     assert np.allclose(got["features"], want["features"], rtol=1e-5, atol=0)
@@ -1156,7 +1159,7 @@ def test_welch_stream_across_epochs(built, n, K, n_epochs, epw):
     for b in range(64):
         cfg.thresh[b] = 1e-3
     iq, picks = signals.make_epochs(cfg, n_epochs, seed=n + K)
-    s = cs.Sensor(cfg)
+    s = forms.sensor(cfg, "streaming")
     s.set_variant(100 + epw)
     got = s.run_host(iq, n_epochs, want_spectrum=True)
     want = orc.run(cfg, iq, n_epochs, want_spectrum=True)
@@ -1174,6 +1177,7 @@ def test_welch_stream_across_epochs(built, n, K, n_epochs, epw):
     got2 = s.run_host(big, n_epochs, epoch_stride=stride)
     want2 = orc.run(cfg, big, n_epochs, epoch_stride=stride)
     assert np.allclose(got2["features"], want2["features"], rtol=1e-5, atol=0)
+    assert s.dealt_launches() == 0
     s.close()
 
 

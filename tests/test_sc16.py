@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 import crnsense as cs
+import forms
 import oracle_py as orc
 
 # The wire-format kernels and their five entry points are OPTIONAL (make -C csrc SC16=1 -> libcrnsense_sc16.so): the default library does
@@ -118,29 +119,35 @@ def test_wire_format_is_bit_identical_to_the_float_path(built, name, cfg, L, wan
     host_f = (raw.astype(np.float32) / np.float32(32768.0)).ravel()                       # UHD's sc16 -> fc32 conversion
     d_raw = torch.from_numpy(raw.copy()).to(dev)
     d_f = torch.from_numpy(host_f).to(dev)
-    s = cs.Sensor(cfg)
     for k in range(cfg.n_bands):
         if np.isfinite(cfg.thresh[k]) and cfg.ref_band < 0:
             cfg.thresh[k] = 1e-3
-    outs = []
-    for _ in range(2):
-        feats = torch.zeros(n, cfg.n_bands, device=dev)
-        ann = torch.zeros(n, 3, dtype=torch.float64, device=dev)
-        dec = torch.full((n,), -7, dtype=torch.int32, device=dev)
-        occ = torch.full((n, cfg.n_bands), 9, dtype=torch.uint8, device=dev)
-        spec = torch.zeros(n, cfg.fft_len, device=dev) if want_spectrum else None
-        outs.append((feats, ann, dec, occ, spec))
-    ptrs = [{"features": o[0].data_ptr(), "ann_out": o[1].data_ptr(), "decision": o[2].data_ptr(), "occupancy": o[3].data_ptr(),
-             "spectrum": o[4].data_ptr() if want_spectrum else 0} for o in outs]
-    s.run_device(d_f.data_ptr(), n, L, ptrs[0])
-    s.run_device(d_raw.data_ptr(), n, L, ptrs[1], sc16=True)
-    torch.cuda.synchronize()
-    for a, b in zip(outs[0], outs[1]):
-        if a is not None:
-            assert torch.equal(a, b)                                                      # bit for bit
     want = orc.run(cfg, host_f, n, L=L)
-    assert np.allclose(outs[1][0].cpu().numpy(), want["features"], rtol=3e-5, atol=0)
+    # 37 epochs: by its own choice the library deals them at 512 / 1024 points.  Both forms, each named (tests/forms.py) and checked to have
+    # run — the streaming one is what large batches run, the dealt one (where the configuration has it) what this launch gets by default
+    for form in ("streaming", "dealt"):
+        s = forms.sensor(cfg, form)
+        outs = []
+        for _ in range(2):
+            feats = torch.zeros(n, cfg.n_bands, device=dev)
+            ann = torch.zeros(n, 3, dtype=torch.float64, device=dev)
+            dec = torch.full((n,), -7, dtype=torch.int32, device=dev)
+            occ = torch.full((n, cfg.n_bands), 9, dtype=torch.uint8, device=dev)
+            spec = torch.zeros(n, cfg.fft_len, device=dev) if want_spectrum else None
+            outs.append((feats, ann, dec, occ, spec))
+        ptrs = [{"features": o[0].data_ptr(), "ann_out": o[1].data_ptr(), "decision": o[2].data_ptr(), "occupancy": o[3].data_ptr(),
+                 "spectrum": o[4].data_ptr() if want_spectrum else 0} for o in outs]
+        s.run_device(d_f.data_ptr(), n, L, ptrs[0])
+        s.run_device(d_raw.data_ptr(), n, L, ptrs[1], sc16=True)
+        torch.cuda.synchronize()
+        forms.assert_ran(s, form, 2, L=L)
+        for a, b in zip(outs[0], outs[1]):
+            if a is not None:
+                assert torch.equal(a, b), form                                                # bit for bit
+        assert np.allclose(outs[1][0].cpu().numpy(), want["features"], rtol=3e-5, atol=0), form
+        s.close()
     # the device packer inverts the conversion exactly
+    s = cs.Sensor(cfg)
     packed = torch.zeros(need, 2, dtype=torch.int16, device=dev)
     s.pack_sc16_device(d_f.data_ptr(), need, packed.data_ptr())
     torch.cuda.synchronize()
