@@ -451,6 +451,86 @@ CRN_API int crn_tracks_carry_device(crn_handle *h, const crn_segment_epoch *d_ep
                                     crn_track_carry_stream *d_streams, crn_track *d_tracks, crn_track *d_open, void *d_workspace,
                                     int64_t workspace_bytes, void *stream);
 
+/* -- channels: occupancy statistics over time and an idle forecast -------------------------------------------------------------
+ * What a cognitive radio senses for: which channel is free, and how likely it is to stay free.  The CFAR bin mask (and, optionally, the
+ * `spectrum` rows) of a batch become one small record per stream and channel: busy fraction, the 2 x 2 transition counts of the
+ * two-state chain idle / busy, run statistics and idle / busy power.  The record lives in the caller's device memory and is its own
+ * carry from call to call.  A batch is laid out as for crn_tracks_device: n_epochs / epochs_per_stream streams of epochs_per_stream
+ * consecutive epochs in time order; N = fft_len.
+ *   Per epoch and channel   n_det = set mask bits inside the span; busy = n_det >= min_bins (a min_bins larger than the width: never
+ *                           busy); power = the sum of P over the span's bins, accumulated in fp64 and rounded to fp32 once (0 when
+ *                           d_spectrum is NULL).  Sums are direct: no bin outside the span ever enters one.
+ *   Per stream and channel  the epochs in time order, s the busy bit and p the fp32 power of each:
+ *       if first: R = all zero
+ *       for each epoch of the stream:
+ *           if R.n_epochs > 0:
+ *               a = R.state & 1
+ *               R.n_trans[a][s] += 1
+ *               if s != a:                          the run (a, R.run) is complete
+ *                   R.n_runs[a] += 1; R.run_sum[a] += R.run; R.run_max[a] = max(R.run_max[a], R.run)
+ *                   if a == 0: R.idle_hist[clamp(floor(log2(max(R.run, 1))), 0, 15)] += 1
+ *                   R.run = 0
+ *           R.state = s; R.run += 1; R.n_epochs += 1; R.n_busy += s; R.power[s] += (double)p
+ *     The first run starts with the first observed epoch (it is left-censored) and is counted when it ends; the run in progress is in
+ *     no completed count.  A record is all zero or what an earlier call wrote; nothing else is told apart from these.
+ *     No index is ever read from a record, so a foreign buffer cannot cause an access outside the buffers.  The four n_trans sum to
+ *     n_epochs - 1, and run_sum[0] + run_sum[1] + run = n_epochs.
+ *   Cut independence        a sequence given in one call and the same sequence cut into several calls (first = 1, then 0) give
+ *                           identical integer fields; d_busy and d_power are the same bytes however the batch is cut.  power[] is an
+ *                           fp64 sum of the fp32 values whose order depends on the cut. */
+#define CRN_MAX_CHANNELS 64
+typedef struct crn_channel_span {
+  int32_t lo, width;
+} crn_channel_span; /* bins (lo + i) mod N, 0 <= i < width; 0 <= lo < N, 1 <= width <= N.  A span may cross the wrap (the reference's
+                     * CH1 does).  Spans may overlap. */
+typedef struct crn_channel_params {
+  int32_t n_channels;        /* 1..64 */
+  int32_t epochs_per_stream; /* >= 1, divides n_epochs */
+  int32_t min_bins;          /* >= 1 */
+  int32_t first;             /* != 0: the records' contents mean nothing, start afresh */
+  int32_t reserved[4];       /* 0 */
+  crn_channel_span span[CRN_MAX_CHANNELS];
+} crn_channel_params; /* 544 bytes */
+typedef struct crn_channel_stats {
+  int64_t n_epochs, n_busy;
+  int64_t n_trans[2][2];                     /* [previous][current], 0 idle, 1 busy */
+  int64_t n_runs[2], run_sum[2], run_max[2]; /* completed runs only */
+  int64_t run;                               /* length so far of the run in progress */
+  int32_t state, reserved;
+  double power[2];                           /* sum of the channel's power over idle / busy epochs */
+  int32_t idle_hist[16];                     /* completed idle runs with floor(log2(length)) = b; bin 15 also takes everything longer */
+} crn_channel_stats; /* 192 bytes */
+
+/* Bytes of device scratch crn_channels_device needs for n_epochs epochs under `params`: needs no handle and no device.  Positive for
+ * valid arguments (also for n_epochs = 0), -1 for a NULL params, n_epochs < 0, n_channels outside 1..64, epochs_per_stream < 1 or not
+ * dividing n_epochs, min_bins < 1, a nonzero reserved field, or a span with lo < 0 or width < 1 or either beyond the largest fft_len. */
+CRN_API int64_t crn_channels_workspace_bytes(int64_t n_epochs, const crn_channel_params *params);
+
+/* Enqueue the reduction on `stream` (device pointers):
+ *   d_bin_mask   [n_epochs][fft_len / 32]      as crn_sense_run_device_cfar writes it (8-byte aligned)
+ *   d_spectrum   [n_epochs][fft_len]           the `spectrum` output of the same launch (16-byte aligned), or NULL: every power is 0
+ *   d_stats      [n_streams][n_channels]       the records (16-byte aligned): read (unless first != 0), then rewritten
+ *   d_busy       [n_epochs] uint64, or NULL    bit c = channel c busy in that epoch (8-byte aligned)
+ *   d_power      [n_epochs][n_channels] fp32, or NULL   (16-byte aligned; refused without d_spectrum)
+ *   d_workspace  workspace_bytes >= crn_channels_workspace_bytes of scratch (8-byte aligned); its contents before and after mean nothing
+ * `h` supplies fft_len and the device, nothing else: the mask and rows may come from any source, the handle may be of any mode, with
+ * CFAR on or off.  Only enqueues (three small launches), allocates nothing, keeps no host state; integer fields do not depend on the
+ * order the work ran in.  CRN_ERR_ARG, decided before any device call, for a NULL h, params, d_bin_mask, d_stats or d_workspace;
+ * n_epochs < 0; n_channels outside 1..64; a span with lo outside 0 .. fft_len - 1 or width outside 1 .. fft_len; min_bins < 1;
+ * epochs_per_stream < 1 or not dividing n_epochs; a nonzero reserved field; d_power without d_spectrum; a misaligned pointer; a
+ * workspace too small.  n_epochs = 0 succeeds and launches nothing, with first != 0 too (the records are then left as they are). */
+CRN_API int crn_channels_device(crn_handle *h, const uint32_t *d_bin_mask, const float *d_spectrum, int64_t n_epochs,
+                                const crn_channel_params *params, crn_channel_stats *d_stats, uint64_t *d_busy, float *d_power,
+                                void *d_workspace, int64_t workspace_bytes, void *stream);
+
+/* A record as a two-state Markov chain, host only (`s` is a host copy of one record):
+ *   p01 = (n_trans[0][1] + prior) / (n_trans[0][0] + n_trans[0][1] + 2 prior), p10 likewise from n_trans[1][.]; a 0 / 0 gives 0.5
+ *   p_idle = the probability that every one of the next `horizon` epochs is idle: (1 - p01)^horizon from an idle state (state & 1 = 0),
+ *            p10 (1 - p01)^(horizon - 1) from a busy one
+ * prior = 1 is Laplace's rule, 0 the plain frequencies.  Any output pointer may be NULL.  CRN_ERR_ARG for a NULL s, horizon < 1, or a
+ * negative or non-finite prior. */
+CRN_API int crn_channel_forecast(const crn_channel_stats *s, int32_t horizon, double prior, double *p01, double *p10, double *p_idle);
+
 /* Allocate, now, the device scratch and pinned staging that crn_sense_run_host needs for up to
  * max_epochs dense epochs of full-length frames (and their per-bin spectra when want_spectrum != 0),
  * and load the kernels: a later crn_sense_run_host within that size allocates nothing.  An engine

@@ -48,6 +48,7 @@ EXPORTS = [
     "crn_sense_set_cfar_ex", "crn_sense_get_cfar_ex", "crn_cfar_alpha_ex",
     "crn_segments_device", "crn_tracks_workspace_bytes", "crn_tracks_device",
     "crn_tracks_carry_bytes", "crn_tracks_carry_workspace_bytes", "crn_tracks_carry_device",
+    "crn_channels_workspace_bytes", "crn_channels_device", "crn_channel_forecast",
     "crn_comm_unique_id", "crn_comm_create", "crn_comm_local", "crn_comm_allgather", "crn_comm_gathered",
     "crn_comm_finish", "crn_comm_destroy", "crn_comm_local_addr", "crn_comm_wait", "crn_comm_info",
     "crn_last_error", "crn_abi_version", "crn_build_info",
@@ -130,6 +131,31 @@ TRACK_HITS_UPPER_BOUND = 4                    # crn_track.flags from crn_tracks_
 # the per-stream header crn_tracks_carry_device writes: (.., TRACK_CARRY_STREAM_DTYPE) [n_streams]
 TRACK_CARRY_STREAM_DTYPE = [("n_found", "<i4"), ("n_stored", "<i4"), ("n_nodes", "<i4"), ("n_open", "<i4"), ("n_open_found", "<i4"),
                             ("n_open_stored", "<i4"), ("status", "<i4"), ("reserved", "<i4")]
+CRN_MAX_CHANNELS = 64
+
+
+class ChannelSpan(C.Structure):
+    """crn_channel_span: bins (lo + i) mod fft_len, 0 <= i < width."""
+    _fields_ = [("lo", C.c_int32), ("width", C.c_int32)]
+
+
+class ChannelParams(C.Structure):
+    """crn_channel_params (crn_channels_device), 544 bytes."""
+    _fields_ = [("n_channels", C.c_int32), ("epochs_per_stream", C.c_int32), ("min_bins", C.c_int32), ("first", C.c_int32),
+                ("reserved", C.c_int32 * 4), ("span", ChannelSpan * CRN_MAX_CHANNELS)]
+
+
+class ChannelStats(C.Structure):
+    """crn_channel_stats: one stream's record of one channel, 192 bytes."""
+    _fields_ = [("n_epochs", C.c_int64), ("n_busy", C.c_int64), ("n_trans", (C.c_int64 * 2) * 2), ("n_runs", C.c_int64 * 2),
+                ("run_sum", C.c_int64 * 2), ("run_max", C.c_int64 * 2), ("run", C.c_int64), ("state", C.c_int32), ("reserved", C.c_int32),
+                ("power", C.c_double * 2), ("idle_hist", C.c_int32 * 16)]
+
+
+# numpy view of the records crn_channels_device keeps: np.frombuffer(bytes, CHANNEL_STATS_DTYPE).reshape(n_streams, n_channels)
+CHANNEL_STATS_DTYPE = [("n_epochs", "<i8"), ("n_busy", "<i8"), ("n_trans", "<i8", (2, 2)), ("n_runs", "<i8", (2,)), ("run_sum", "<i8", (2,)),
+                       ("run_max", "<i8", (2,)), ("run", "<i8"), ("state", "<i4"), ("reserved", "<i4"), ("power", "<f8", (2,)),
+                       ("idle_hist", "<i4", (16,))]
 CFAR_METHODS = {"ca": CFAR_CA, "go": CFAR_GO, "so": CFAR_SO, "os": CFAR_OS}
 
 
@@ -254,6 +280,10 @@ def lib():
             f.argtypes, f.restype = [C.c_int64, C.POINTER(TrackParams)], C.c_int64
         L.crn_tracks_carry_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(TrackParams), C.c_int64, C.c_int32, C.c_void_p,
                                               C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+        L.crn_channels_workspace_bytes.argtypes, L.crn_channels_workspace_bytes.restype = [C.c_int64, C.POINTER(ChannelParams)], C.c_int64
+        L.crn_channels_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(ChannelParams), C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.c_void_p, C.c_int64, C.c_void_p]
+        L.crn_channel_forecast.argtypes = [C.c_void_p, C.c_int32, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]
         L.crn_ingest_create.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]
         L.crn_ingest_push.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
         L.crn_ingest_flush.argtypes = [C.c_void_p]
@@ -417,6 +447,79 @@ def track_hz(centre, width_sum, n_segments, fft_len, fs, fc):
     mean position of the members), the bandwidth is the members' mean width, width_sum / n_segments bins; the mapping of bins to hertz
     is segment_hz's."""
     return segment_hz(0, float(width_sum) / max(int(n_segments), 1), centre, fft_len, fs, fc)
+
+
+def channel_params(spans, epochs_per_stream, min_bins=1, first=False):
+    """crn_channel_params from a list of (lo, width) pairs or ChannelSpan."""
+    spans = [(sp.lo, sp.width) if isinstance(sp, ChannelSpan) else (int(sp[0]), int(sp[1])) for sp in spans]
+    if len(spans) > CRN_MAX_CHANNELS:
+        raise ValueError(f"at most {CRN_MAX_CHANNELS} channels, not {len(spans)}")
+    q = ChannelParams(n_channels=len(spans), epochs_per_stream=int(epochs_per_stream), min_bins=int(min_bins), first=int(bool(first)))
+    for c, (lo, width) in enumerate(spans):
+        q.span[c].lo, q.span[c].width = lo, width
+    return q
+
+
+def channels_workspace_bytes(n_epochs, spans, epochs_per_stream=None, min_bins=1):
+    """Bytes of device scratch Sensor.channels_device needs (crn_channels_workspace_bytes): no handle, no device."""
+    q = channel_params(spans, n_epochs if epochs_per_stream is None else epochs_per_stream, min_bins)
+    nb = lib().crn_channels_workspace_bytes(int(n_epochs), C.byref(q))
+    if nb <= 0:
+        raise CrnError(f"crn_channels_workspace_bytes: arguments out of range ({nb})")
+    return nb
+
+
+def channel_spans_from_bands(cfg):
+    """[ChannelSpan] per band of a plan whose bands are single circular intervals (crn_cfg_welch's are): one segment, or two that meet
+    at the wrap (one ends at fft_len, the other begins at 0).  ValueError for any other plan."""
+    spans = []
+    for b in range(cfg.n_bands):
+        segs = sorted((cfg.segs[i].lo, cfg.segs[i].hi) for i in range(cfg.n_segs) if cfg.segs[i].band == b and cfg.segs[i].hi > cfg.segs[i].lo)
+        if len(segs) == 1:
+            lo, width = segs[0][0], segs[0][1] - segs[0][0]
+        elif len(segs) == 2 and segs[0][0] == 0 and segs[1][1] == cfg.fft_len and segs[0][1] <= segs[1][0]:
+            lo, width = segs[1][0], segs[1][1] - segs[1][0] + segs[0][1]
+        else:
+            raise ValueError(f"band {b} is not one circular interval: {segs}")
+        spans.append(ChannelSpan(lo=lo % cfg.fft_len, width=width))
+    return spans
+
+
+def _channel_stats(row):
+    """A ChannelStats from one numpy record of CHANNEL_STATS_DTYPE (or a ChannelStats)."""
+    if isinstance(row, ChannelStats):
+        return row
+    import numpy as np
+    raw = np.asarray(row, dtype=np.dtype(CHANNEL_STATS_DTYPE)).tobytes()
+    if len(raw) != C.sizeof(ChannelStats):
+        raise ValueError("channel_forecast takes ONE record of CHANNEL_STATS_DTYPE")
+    return ChannelStats.from_buffer_copy(raw)
+
+
+def channel_forecast(stats_row, horizon, prior=1.0):
+    """(p01, p10, p_idle) of one record (crn_channel_forecast): the two-state chain's transition probabilities with `prior` added to
+    every count, and the probability that the next `horizon` epochs are all idle."""
+    st = _channel_stats(stats_row)
+    p01, p10, pi = C.c_double(), C.c_double(), C.c_double()
+    check(lib().crn_channel_forecast(C.byref(st), int(horizon), float(prior), C.byref(p01), C.byref(p10), C.byref(pi)), "crn_channel_forecast")
+    return p01.value, p10.value, pi.value
+
+
+def best_channel(stats_of_stream, horizon, prior=1.0, widths=None):
+    """The channel of one stream's records most likely to stay idle for `horizon` epochs: the argmax of p_idle.  Ties go to the lower mean
+    idle power per bin (power[0] over the idle epochs, over widths[c] when given; a channel never seen idle counts as the loudest), then to
+    the lower index."""
+    best = None
+    for c, row in enumerate(stats_of_stream):
+        st = _channel_stats(row)
+        idle = st.n_epochs - st.n_busy
+        quiet = st.power[0] / idle / (widths[c] if widths is not None else 1) if idle > 0 else float("inf")
+        key = (-channel_forecast(st, horizon, prior)[2], quiet, c)
+        if best is None or key < best:
+            best = key
+    if best is None:
+        raise ValueError("best_channel: no records")
+    return best[2]
 
 
 def save_ann(cfg, path):
@@ -636,6 +739,17 @@ class Sensor:
                                             v(carry_ptr), carry_bytes, v(streams_ptr), v(tracks_ptr), v(open_ptr), v(workspace_ptr),
                                             workspace_bytes, v(stream)),
               "crn_tracks_carry_device")
+
+    def channels_device(self, mask_ptr, spectrum_ptr, n_epochs, stats_ptr, workspace_ptr, workspace_bytes, spans, epochs_per_stream=None,
+                        min_bins=1, first=False, busy_ptr=0, power_ptr=0, stream=0):
+        """Per-channel occupancy records from n_epochs rows of a CFAR bin mask and, unless spectrum_ptr is 0, the matching `spectrum` rows
+        (device pointers): stats_ptr [n_streams][len(spans)] CHANNEL_STATS_DTYPE, read (unless `first`) and rewritten; busy_ptr [n_epochs]
+        uint64 or 0; power_ptr [n_epochs][len(spans)] float32 or 0; workspace_ptr at least channels_workspace_bytes(...) of scratch;
+        n_streams = n_epochs / epochs_per_stream (one stream when None).  Only enqueues."""
+        q = channel_params(spans, n_epochs if epochs_per_stream is None else epochs_per_stream, min_bins, first)
+        v = lambda ptr: C.c_void_p(ptr or None)      # noqa: E731
+        check(lib().crn_channels_device(self._h, v(mask_ptr), v(spectrum_ptr), n_epochs, C.byref(q), v(stats_ptr), v(busy_ptr), v(power_ptr),
+                                        v(workspace_ptr), int(workspace_bytes), v(stream)), "crn_channels_device")
 
     def set_wire_full_scale(self, full_scale):
         _need_sc16("set_wire_full_scale")
