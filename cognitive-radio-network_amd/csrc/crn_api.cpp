@@ -184,16 +184,19 @@ int crn_sense_kernel_info(crn_handle *h, char *name, int32_t name_len, int32_t *
                        &nbuf, &pf, &nt, &tl, &pk);
     const bool plain4096 = h->cfg.fft_len == 4096 && h->cfg.mode != CRN_MODE_REF_MAG && h->cfg.window == CRN_WINDOW_RECT;
     // what a launch without a spectrum output runs (a spectrum request falls back to full rows / the LDS close)
-    bool reg_close = h->n_row_entries > 0 && h->cfg.window == CRN_WINDOW_RECT;
+    // (the plain 4096-point kernel labels its register rows 7 bins early — crn_kernels.h, bin_of — and is judged by the plan cut at those rows)
+    const int n_rows_ent = plain4096 ? h->n_row_entries_shift : h->n_row_entries;
+    const unsigned plan_mask = plain4096 ? h->acc_mask_shift : h->acc_mask;
+    bool reg_close = n_rows_ent > 0 && h->cfg.window == CRN_WINDOW_RECT;
     if (plain4096) {  // the forms of the plain kernel that carry the register close
       const int v = h->variant == 0 ? 13 : h->variant;
-      const bool rows_ok = (h->acc_mask & ~0x8267u) == 0;
+      const bool rows_ok = (plan_mask & ~0x8267u) == 0;
       reg_close = reg_close && (v == 2 || v == 13 || v == 17 || (v == 7 && rows_ok));
     }
     // pass 3 / accumulate pruned to the reference channel plan's registers: the plain 4096-point kernel's default form, and the
     // register-close kernels of every other size and mode (what a launch without a spectrum output runs)
     const unsigned ref_mask = crn::sense_ref_acc_mask(h->cfg.fft_len);
-    const bool inside = (h->acc_mask & ~ref_mask) == 0 && ref_mask != 0xFFFFu && h->variant != 2;
+    const bool inside = (plan_mask & ~ref_mask) == 0 && ref_mask != 0xFFFFu && h->variant != 2;   // (N = 4096: the same seven rows in both labellings)
     const bool pruned = reg_close && inside && h->cfg.window == CRN_WINDOW_RECT && (!plain4096 || h->variant == 0 || h->variant == 13);
     // periodic Hann in energy mode: the window is folded into pass 1 (whole frames); with the Welch scan's plan
     // (N = 4096, equal contiguous bands) the close forms band sums by DPP
@@ -376,6 +379,9 @@ static int run_device_impl(crn_handle *h, const void *d_iq, int64_t n_epochs, in
     p.wire_unscale = (float)(c.mode == CRN_MODE_REF_MAG ? u : u * u);
   }
   p.n_row_entries = h->n_row_entries;
+  p.row_entries_shift = h->d_row_entries_shift;
+  p.n_row_entries_shift = h->n_row_entries_shift;
+  p.acc_mask_shift = h->variant == 2 ? 0xFFFFu : h->acc_mask_shift;
   p.features = d_out->features;
   // (a measurement form that writes time stamps puts them there: libcrnsense_ab.so only)
   p.ann_out = (c.decide == CRN_DECIDE_ANN || crn::sense_variant_traces(h->variant)) ? d_out->ann_out : nullptr;

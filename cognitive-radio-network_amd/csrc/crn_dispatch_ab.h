@@ -33,7 +33,7 @@ static bool launch_measurement_form(const SenseParams &p, bool mag, bool win, in
     }
     if (!win && (variant == 7 || variant == 17)) {
       constexpr int kPlain = kSpread | kLdsBlk | kTw1C | kMulti;
-      const bool ref_rows = reg_bands(p) && (p.acc_mask & ~kRefPlanRows) == 0;
+      const bool ref_rows = ref_plan_rows_shift(p);
       if (variant == 17) *e = launch_rn<R3, 1, true, true, true, 4, true, kPlain | kRows | kPrioValu | kRegBands | kTrace>(p, mag, win, stream);
       else *e = ref_rows ? launch_rn<R3, 1, true, true, true, 4, true, kPlain | kRows | kRegBands>(p, mag, win, stream)
                          : launch_rn<R3, 1, true, true, true, 4, true, kPlain>(p, mag, win, stream);

@@ -242,8 +242,9 @@ CRN_DEV void epoch_close(FrameCtx<C> &c, const SenseParams &p, long long epoch_b
   } else if constexpr ((C::OPT & kRegBands) != 0) {
     // Band sums straight from the accumulator registers: no LDS image of the spectrum, no barrier
     // before it (nothing aliases the exchange buffers) and none after the decision.  Thread bins are
-    // base_j + 256 d; the host cut the band plan at the 256-bin rows (crn_tables.cpp), so each entry is
-    // (row d, band, [lo, hi) in the row): masked add over j, DPP team sum, lane `band` keeps it.
+    // row_start(d) + q_j (BinMap: row_start = 256 d, 256 d - 7 in the kTw1C kernels); the host cut the band
+    // plan at those rows (crn_tables.cpp), so each entry is (row d, band, [lo, hi) in the row): masked add over j,
+    // DPP team sum, lane `band` keeps it.
     // LDS round trips are what this block avoids (an LDS read here queues behind the exchange
     // traffic of the CU's other waves: measured ~500 ticks each): the entries come through the
     // scalar cache, the features stay in lanes, the thresholds are fetched first and used last.
@@ -266,14 +267,18 @@ CRN_DEV void epoch_close(FrameCtx<C> &c, const SenseParams &p, long long epoch_b
     };
     constexpr int kFirst = next_live(-1);
     float fsum = 0.f;
-    typename SWords<CAP>::T ent_next = s_load_row<CAP, (kTabRowEntries + kFirst * CAP) * 4>(p.band_tab);
+    // (the kTw1C kernels read the entries cut at their own rows: same packing, a table of their own)
+    constexpr bool SHIFTED = BinMap<C>::S != 0;
+    constexpr int kEnt0 = SHIFTED ? 0 : kTabRowEntries;
+    const int *ent_tab = SHIFTED ? p.row_entries_shift : p.band_tab;
+    typename SWords<CAP>::T ent_next = s_load_row<CAP, (kEnt0 + kFirst * CAP) * 4>(ent_tab);
     static_for<R3>([&](auto dc) {
       constexpr int d = decltype(dc)::value;
       if constexpr (row_live(d)) {
         typename SWords<CAP>::T ent = ent_next;
         s_wait_row(ent);
         constexpr int dn = next_live(d);
-        if constexpr (dn < R3) ent_next = s_load_row<CAP, (kTabRowEntries + dn * CAP) * 4>(p.band_tab);
+        if constexpr (dn < R3) ent_next = s_load_row<CAP, (kEnt0 + dn * CAP) * 4>(ent_tab);
 #pragma unroll
         for (int e = 0; e < CAP; e++) {
           const int w = ent[e];
@@ -283,7 +288,7 @@ CRN_DEV void epoch_close(FrameCtx<C> &c, const SenseParams &p, long long epoch_b
 #pragma unroll
             for (int j = 0; j < J; j++) {
               if (((AM >> (j * R3 + d)) & 1u) == 0) continue;   // never accumulated: no band of the plan reaches it
-              const int base = a + 16 * (m_lo * J + j);
+              const int base = BinMap<C>::q(a, m_lo, j);
               v += (unsigned)(base - lo) < (unsigned)span ? acc[j * R3 + d] : 0.f;
             }
             v = team_sum<TEAM>(v, tid);
@@ -356,7 +361,10 @@ CRN_DEV void epoch_close(FrameCtx<C> &c, const SenseParams &p, long long epoch_b
       for (int d = 0; d < R3; d++) {
         // the pruned kernels never accumulate (or read back) the other registers
         if (((acc_mask<C>() >> (j * R3 + d)) & 1u) == 0) continue;
-        const int k = a + 16 * (m_lo * J + j) + 256 * d;
+        // (S = 0 is written out where it has always stood: formed through the helper, the same value compiles to other instructions in
+        // the twelve 4096-point kernels that close through this walk without kTw1C — tools/isa_diff.py)
+        int k = a + 16 * (m_lo * J + j) + 256 * d;   // = bin_of<0>(lane_coord<0>(a, m_lo, j, J), d, N)
+        if constexpr (BinMap<C>::S != 0) k = BinMap<C>::bin(a, m_lo, j, d);
         spec[spec_phys(k)] = acc[j * R3 + d];
       }
 #pragma unroll

@@ -144,10 +144,34 @@ struct Cfg {
   static constexpr unsigned SB = SC16 ? 4u : 8u;       // bytes per complex sample in HBM
 };
 
+// Which bin a thread's accumulator register holds (crn_kernels.h: lane_coord / bin_of, shared with the host's row entries): the one
+// place the kernels derive it.  Forms without kTw1C have S = 0, the plain a + 16 (m_lo J + j) + 256 d.
+template <class C>
+struct BinMap {
+  static constexpr int S = (C::OPT & kTw1C) != 0 ? kTw1cRowShift : 0;
+  static_assert(S == 0 || C::R3 == 16, "the compressed pass-1 table exists at N = 4096");
+  CRN_DEV constexpr int q(int a, int m_lo, int j) { return lane_coord<S>(a, m_lo, j, Geo<C::R3>::J); }   // register row j R3 + .: its offset in a 256-bin row
+  CRN_DEV constexpr int bin(int a, int m_lo, int j, int d) { return bin_of<S>(q(a, m_lo, j), d, Geo<C::R3>::N); }
+};
+// The reference channel plan's registers under that map: ref_acc_mask with every bin moved up by S.
+constexpr unsigned ref_acc_mask_shifted(int R3, int S) {
+  const int seg[5][2] = {{0, 16}, {496, 511}, {55, 85}, {189, 222}, {300, 310}};   // as in ref_acc_mask (crn_butterflies.h)
+  const int J = 16 / R3, Sc = R3 / 2, N = 256 * R3;
+  unsigned mask = 0;
+  for (int s = 0; s < 5; s++)
+    for (int k = seg[s][0] * Sc; k < seg[s][1] * Sc; k++) {
+      const int ks = (k + S) & (N - 1);
+      mask |= 1u << ((((ks & 255) >> 4) % J) * R3 + (ks >> 8));
+    }
+  return mask;
+}
+static_assert(ref_acc_mask_shifted(16, 0) == kRefPlanRows && ref_acc_mask_shifted(2, 0) == ref_acc_mask(2), "S = 0: ref_acc_mask itself");
+static_assert(ref_acc_mask_shifted(16, kTw1cRowShift) == kRefPlanRows, "N = 4096: the plan reaches the same seven rows when they start 7 bins early");
+
 // Per-thread state that lives across the frames of an epoch.
 template <class C>
 struct FrameCtx {
-  cx tw1[16];   // W_N^{t i}
+  cx tw1[16];   // W_N^{t i} (kTw1C: [1, 8] only)
   cx tw2[16];   // W_T^{m_lo i} (registers unless TW2LDS)
   float win[16];
   cx winp[4];   // kHannSym: (w[2p], w[2p + 1]) of rows 0..7
@@ -201,11 +225,12 @@ CRN_DEV void ph_pass1(cx (&u)[16], cx (&v)[16], FrameCtx<C> &c, const Hook &hook
     dft16<C::PK>(u, v, hook);
   }
   if constexpr ((C::OPT & kTw1C) != 0) {
-    // compressed table: tw1[1..8] = W^{t i}, tw1[0] = W^{16 t}; W^{t (16-i)} = W^{16 t} conj(W^{t i})
+    // compressed table: tw1[1..8] = W^{t i}.  Rows 9..15 are taken as the negative frequencies i - 16 (DFT16's output index is periodic):
+    // their twiddle W^{t (i - 16)} = conj(W^{t (16 - i)}) is in the table, and the thread's bins are labelled accordingly (BinMap)
 #pragma unroll
     for (int i = 1; i <= 8; i++) v[i] = m::mul(v[i], c.tw1[i]);
 #pragma unroll
-    for (int i = 9; i < 16; i++) v[i] = m::mul_conj(m::mul(v[i], c.tw1[0]), c.tw1[16 - i]);
+    for (int i = 9; i < 16; i++) v[i] = m::mul_conj(v[i], c.tw1[16 - i]);
   } else {
 #pragma unroll
     for (int i = 1; i < 16; i++) v[i] = m::mul(v[i], c.tw1[i]);
@@ -342,7 +367,7 @@ CRN_DEV void ph_x2_read(cx (&u)[16], cx *buf, FrameCtx<C> &c) {
 #pragma unroll
     for (int mm = 0; mm < R3; mm++) u[j * R3 + mm] = row[(c.m_lo * J + j) * R3 + mm + c.m_lo];
 }
-// pass 3: DFT_R3 over m_lo -> d; bin k = a + 16 (g J + j) + 256 d; then the per-bin accumulate
+// pass 3: DFT_R3 over m_lo -> d; bin k = a + 16 (g J + j) + 256 d (kTw1C: a - 16 for a >= 9, BinMap); then the per-bin accumulate
 // over the epoch (reference: fft_avg[i] += cabsf(X[i]) / K, CE_Predictive_Node.cpp:152-154)
 template <class C>
 CRN_DEV void ph_pass3(cx (&u)[16], cx (&v)[16]) {
@@ -376,10 +401,11 @@ CRN_DEV void ph_pass3(cx (&u)[16], cx (&v)[16]) {
   }
 }
 
-// Accumulator registers a kernel keeps: all 16, or (kRows) those that can hold a bin of the reference channel plan.
+// Accumulator registers a kernel keeps: all 16, or (kRows) those that can hold a bin of the reference channel plan under the kernel's bin map.
 template <class C>
 constexpr unsigned acc_mask() {
-  return (C::OPT & kRows) != 0 ? ref_acc_mask(C::R3) : 0xFFFFu;
+  if ((C::OPT & kRows) == 0) return 0xFFFFu;
+  return (C::OPT & kTw1C) != 0 ? ref_acc_mask_shifted(C::R3, kTw1cRowShift) : ref_acc_mask(C::R3);
 }
 
 // pass 3 restricted to the outputs named in MASK (bit j R3 + d); what it forms is what ph_pass3 forms, bit for bit
@@ -470,7 +496,7 @@ CRN_DEV void replay_parked(FrameCtx<C> &c, unsigned park_base, int K) {
   }
 }
 
-// pass 3 + per-bin accumulate: v[j * R3 + d] is bin a + 16 (m_lo J + j) + 256 d
+// pass 3 + per-bin accumulate: v[j * R3 + d] is bin BinMap<C>::bin(a, m_lo, j, d)
 template <class C>
 CRN_DEV void ph_pass3_acc(cx (&u)[16], FrameCtx<C> &c) {
   if constexpr ((C::OPT & kDeal) != 0) {

@@ -26,6 +26,9 @@ struct crn_handle {
   int n_cus = 256;              // compute units of the device (workgroup slots = n_cus x workgroups per CU): read at creation
   size_t lds_budget = 64 * 1024;   // LDS a workgroup may ask for on this device (hipDeviceAttributeMaxSharedMemoryPerBlock: 160 KiB on gfx950)
   unsigned acc_mask = 0xFFFFu;  // accumulator registers (bit j R3 + d) that hold a bin of some band (N = 4096: the 256-bin rows)
+  // the plan as the plain 4096-point kernels see it (register rows 7 bins early: crn_kernels.h, bin_of): their row entries and mask
+  int n_row_entries_shift = 0;
+  unsigned acc_mask_shift = 0xFFFFu;
   bool cfar_on = false;         // crn_sense_set_cfar[_ex]: per-bin CFAR decides instead of the cfg's rule (under tables_mu)
   crn_cfar_params_ex cfar{};    // the detector last set (crn_sense_set_cfar: method CA, rank 0)
   // one device slab holding every table
@@ -33,7 +36,7 @@ struct crn_handle {
   const float2 *d_tw1 = nullptr, *d_tw2 = nullptr;
   const float *d_window = nullptr, *d_thresh = nullptr;
   const int *d_band_seg_begin = nullptr, *d_seg_lo = nullptr, *d_seg_hi = nullptr;
-  const int *d_band_bins_begin = nullptr, *d_band_bins = nullptr, *d_band_tab = nullptr, *d_band_c2 = nullptr;
+  const int *d_band_bins_begin = nullptr, *d_band_bins = nullptr, *d_band_tab = nullptr, *d_band_c2 = nullptr, *d_row_entries_shift = nullptr;
   const double *d_wih = nullptr, *d_who = nullptr;
   // scratch of crn_sense_run_host
   void *d_scratch = nullptr;

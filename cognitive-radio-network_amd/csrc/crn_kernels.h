@@ -20,6 +20,26 @@ static_assert(kTabSegBegin + kTabSegBeginWords <= kTabSegLo && kTabSegLo + kTabS
               kTabThresh + kTabThreshWords <= kTabRowEntries && kTabRowEntries + kRowEntryWords <= kTabWih && kTabWih % 2 == 0 &&
               kTabWih + kTabWihWords <= kTabWho && kTabWho + kTabWhoWords <= kBandTabWords, "band_tab: regions in order, disjoint, inside the table");
 
+// Which bin an accumulator register holds after pass 3, stated once for the kernels and the host tables.  Thread (a, g) — a = t / R3 the
+// pass-1 row, g = t % R3 — holds in register j R3 + d (J = 16 / R3, j < J, d < R3) the bin
+//   bin_of<S>(q, d) = 256 d - S + q (mod N),  q = lane_coord<S>(a, g, j) = ((a + S) & 15) + 16 (g J + j) in 0..255.
+// S = 0 is the plain labelling a + 16 (g J + j) + 256 d.  The kernels that keep their pass-1 twiddles compressed (kTw1C, crn_frame.h) run
+// pass-1 rows 9..15 as the negative frequencies a - 16 (a 16-point DFT's output index is periodic, and W_N^{t (a - 16)} is the conjugate
+// of a stored twiddle), so their register row d covers bins [256 d - 7, 256 d + 249): S = kTw1cRowShift, the same offset for every lane.
+constexpr int kTw1cRowShift = 7;
+// (S is a template argument and the S = 0 branch the only code those instantiations hold: in the kernels the plain forms must stay the
+// expression they have always been — a branch on a function argument, folded later, compiled the 4096-point LDS close differently)
+template <int S>
+constexpr int lane_coord(int a, int g, int j, int J) {
+  if constexpr (S == 0) return a + 16 * (g * J + j);
+  else return ((a + S) & 15) + 16 * (g * J + j);
+}
+template <int S>
+constexpr int bin_of(int q, int d, int N) {
+  if constexpr (S == 0) return q + 256 * d;
+  else return (q + 256 * d - S) & (N - 1);
+}
+
 enum { CRN_DECIDE_ANN_K = 0, CRN_DECIDE_THRESHOLD_K = 1, CRN_DECIDE_NONE_K = 2 };  // == crn_decide
 enum { CRN_CFAR_CA_K = 0, CRN_CFAR_GO_K = 1, CRN_CFAR_SO_K = 2, CRN_CFAR_OS_K = 3 };     // == crn_cfar_method
 
@@ -77,6 +97,11 @@ struct SenseParams {
   int32_t *cfar_band_bins; // [n_epochs][n_bands] or null: detected bins per band (segment listings counted as the band sums count them)
   int cfar_method;         // crn_cfar_method (crn_sense_set_cfar_ex)
   int cfar_rank;           // OS: detected when at least this many training cells c have fl32(cfar_scale c) < sum_K P[k]
+  // The band plan once more for the kTw1C kernels, whose register rows start kTw1cRowShift bins early (bin_of above): read by them in
+  // place of n_row_entries, band_tab's row entries and acc_mask — which stay what every other kernel reads.
+  const int *row_entries_shift;  // [kRowEntryWords] device; band_tab's row-entry packing, rows cut at ((k + 7) mod N) >> 8, lo / hi from 256 d - 7
+  int n_row_entries_shift;       // > 0: the plan fits those slots (register close of the kTw1C kernels)
+  unsigned acc_mask_shift;       // acc_mask for those rows (N = 4096: bit d = bins [256 d - 7, 256 d + 249) mod N hold a band bin)
 };
 
 struct SynthParams {

@@ -103,8 +103,9 @@ static hipError_t launch_r(const SenseParams &p, bool mag, bool win, int variant
   if (R3 != 16 || mag || p.L != Geo<R3>::N) return launch_default<R3, 1, true, true, false, 3, true, kBase, 1, true, R3 != 16>(p, mag, win, stream);
   if constexpr (R3 == 16) {
     constexpr int kPlain = kSpread | kLdsBlk | kTw1C | kMulti | kPrioValu;
-    const bool regb = reg_bands(p);
-    if (variant != 2 && regb && (p.acc_mask & ~kRefPlanRows) == 0)   // the reference channel plan's rows only (the default, 13)
+    // (kTw1C: these kernels' register rows start 7 bins early — BinMap — so the plan is judged by the entries and the mask cut at those rows)
+    const bool regb = reg_bands_shift(p);
+    if (variant != 2 && ref_plan_rows_shift(p))   // the reference channel plan's rows only (the default, 13)
       return launch_rn<R3, 1, true, true, true, 4, true, kPlain | kRows | kRegBands>(p, mag, win, stream);
     // another plan, a per-bin spectrum request, or variant 2: no pruning
     if (regb) return launch_rn<R3, 1, true, true, true, 4, true, kPlain | kRegBands>(p, mag, win, stream);

@@ -33,9 +33,9 @@ static hipError_t launch_r_sc16(const SenseParams &p, bool mag, bool win, int va
   }
   if constexpr (R3 == 16) {
     if (!mag && p.L == Geo<R3>::N) {
-      if (reg_bands(p) && (p.acc_mask & ~kRefPlanRows) == 0)
+      if (ref_plan_rows_shift(p))   // (the kTw1C kernels' own rows: crn_sense_kernel.h)
         return launch_rn<R3, 1, true, true, true, 4, true, kBase | kTw1C | kRows | kRegBands>(p, mag, win, stream);
-      if (reg_bands(p)) return launch_rn<R3, 1, true, true, true, 4, true, kBase | kTw1C | kRegBands>(p, mag, win, stream);
+      if (reg_bands_shift(p)) return launch_rn<R3, 1, true, true, true, 4, true, kBase | kTw1C | kRegBands>(p, mag, win, stream);
       return launch_rn<R3, 1, true, true, true, 4, true, kBase | kTw1C>(p, mag, win, stream);
     }
   }

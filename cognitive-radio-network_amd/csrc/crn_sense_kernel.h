@@ -89,7 +89,6 @@ __global__ __launch_bounds__(256, C::OCC) void sense_kernel(const SenseParams p)
   // frame-invariant twiddles, kept in registers across frames and epochs
 #pragma unroll
   for (int i = 1; i < ((C::OPT & kTw1C) != 0 ? 9 : 16); i++) c.tw1[i] = reinterpret_cast<const cx *>(p.tw1)[i * T + t];
-  if constexpr ((C::OPT & kTw1C) != 0) c.tw1[0] = reinterpret_cast<const cx *>(p.tw1)[16 * T + t];  // W_N^{16 t}
   // (register-resident tables are requested ahead of the barrier too: nothing after it starts another round trip)
   if constexpr (!C::TW2LDS) {
 #pragma unroll
@@ -390,6 +389,10 @@ static hipError_t launch_dealt_win(const SenseParams &p, hipStream_t stream) {
 // The register form of the epoch close applies to band plans the host could cut into row entries
 // (crn_tables.cpp) when no per-bin spectrum is stored.
 static bool reg_bands(const SenseParams &p) { return p.n_row_entries > 0 && p.spectrum == nullptr; }
+// The same two questions for the kTw1C kernels (the plain 4096-point forms), whose register rows start kTw1cRowShift bins early: the
+// entries cut at those rows, and the reference plan's rows among them (ref_acc_mask_shifted: the same seven).
+static bool reg_bands_shift(const SenseParams &p) { return p.n_row_entries_shift > 0 && p.spectrum == nullptr; }
+static bool ref_plan_rows_shift(const SenseParams &p) { return reg_bands_shift(p) && (p.acc_mask_shift & ~ref_acc_mask_shifted(16, kTw1cRowShift)) == 0; }
 // ... and pass 3 / the accumulate keep only the reference channel plan's registers when every band bin sits in one of them.
 template <int R3>
 static bool ref_plan_rows(const SenseParams &p) { return reg_bands(p) && ref_acc_mask(R3) != 0xFFFFu && (p.acc_mask & ~ref_acc_mask(R3)) == 0; }

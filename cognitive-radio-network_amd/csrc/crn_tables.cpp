@@ -134,6 +134,42 @@ int crn::build_tables(crn_handle *h, const crn_cfg &cfg) {
     }
   }
 
+  // The same once more for the kernels whose register rows start kTw1cRowShift bins early (crn_kernels.h: bin_of — the plain 4096-point
+  // forms): every segment moved up by the shift, wrapped at N, cut at the 256-bin rows of THAT numbering; lo / hi count from the row's
+  // start, i.e. they are the lane coordinates (lane_coord) the kernel compares.  A table of its own: the entries above stay what every
+  // other kernel reads.  Band order, table order inside a band, a wrapped segment's upper part first.
+  std::vector<int> row_entries_shift(crn::kRowEntryWords, 0);
+  int n_row_entries_shift = 0;
+  unsigned acc_mask_shift = 0;
+  {
+    const int S = crn::kTw1cRowShift, J = 16 / R3, cap = crn::kRowEntryWords / R3;
+    struct RowPiece { int d, band, lo, hi; };
+    std::vector<RowPiece> pieces;
+    auto cut = [&](int band, int lo, int hi) {   // [lo, hi) in shifted numbering, inside [0, N)
+      for (int d = lo >> 8; lo < hi && d <= (hi - 1) >> 8; d++)
+        pieces.push_back({d, band, std::max(lo, 256 * d) - 256 * d, std::min(hi, 256 * (d + 1)) - 256 * d});
+    };
+    for (int b = 0; b < cfg.n_bands; b++)
+      for (int sg = seg_begin[b]; sg < seg_begin[b + 1]; sg++) {
+        const int lo = seg_lo[sg] + S, hi = seg_hi[sg] + S;
+        cut(b, std::min(lo, N), std::min(hi, N));
+        cut(b, std::max(lo, N) - N, std::max(hi, N) - N);
+        for (int k = seg_lo[sg]; k < seg_hi[sg]; k++) {
+          const int ks = (k + S) & (N - 1);
+          acc_mask_shift |= 1u << ((((ks & 255) >> 4) % J) * R3 + (ks >> 8));
+        }
+      }
+    bool fits = cfg.n_bands <= 16 && !pieces.empty();
+    std::vector<int> used(16, 0);
+    for (const RowPiece &pc : pieces)
+      if (++used[pc.d] > cap) fits = false;
+    if (fits) {
+      std::fill(used.begin(), used.end(), 0);
+      for (const RowPiece &pc : pieces) row_entries_shift[pc.d * cap + used[pc.d]++] = (pc.band << 18) | (pc.lo << 9) | pc.hi;
+      n_row_entries_shift = (int)pieces.size();
+    }
+  }
+
   // twice the signed centre of every band (bins >= N / 2 are negative frequencies; lowest + highest signed bin, so a band with a
   // small gap in it — the reference plan's CH1 skips bins -1, -2 — is centred on its span): the carrier of the generator's
   // modulated signal kinds
@@ -163,6 +199,7 @@ int crn::build_tables(crn_handle *h, const crn_cfg &cfg) {
       {cfg.ann_w_ho, sizeof(cfg.ann_w_ho), 0},
       {band_tab.data(), band_tab.size() * sizeof(int), 0},
       {band_c2.data(), band_c2.size() * sizeof(int), 0},
+      {row_entries_shift.data(), row_entries_shift.size() * sizeof(int), 0},
   };
   size_t total = 0;
   for (auto &p : parts) {
@@ -186,6 +223,8 @@ int crn::build_tables(crn_handle *h, const crn_cfg &cfg) {
   h->aligned_shift = aligned_shift;
   h->n_row_entries = n_row_entries;
   h->acc_mask = acc_mask;
+  h->n_row_entries_shift = n_row_entries_shift;
+  h->acc_mask_shift = acc_mask_shift;
   h->d_tables = slab;
   char *base = static_cast<char *>(h->d_tables);
   h->d_tw1 = reinterpret_cast<const float2 *>(base + parts[0].off);
@@ -201,5 +240,6 @@ int crn::build_tables(crn_handle *h, const crn_cfg &cfg) {
   h->d_who = reinterpret_cast<const double *>(base + parts[10].off);
   h->d_band_tab = reinterpret_cast<const int *>(base + parts[11].off);
   h->d_band_c2 = reinterpret_cast<const int *>(base + parts[12].off);
+  h->d_row_entries_shift = reinterpret_cast<const int *>(base + parts[13].off);
   return CRN_OK;
 }
