@@ -7,8 +7,8 @@
 #include <string>
 #include <vector>
 
+#include "crn_forms.h"
 #include "crn_handle.h"
-#include "crn_kernels.h"
 #include "crn_segments.h"
 
 namespace crn {
@@ -169,48 +169,33 @@ int crn_sense_set_variant(crn_handle *h, int32_t variant) {
   return CRN_OK;
 }
 
+// What select_form needs to know of the handle's band plan, window and CFAR state: the same for a launch and for crn_sense_kernel_info.
+static void fill_plan_facts(const crn_handle *h, bool spectrum, crn::SenseParams &p) {
+  p.hann_sym = h->cfg.window == CRN_WINDOW_HANN;
+  p.aligned_shift = spectrum ? 0 : h->aligned_shift;
+  p.acc_mask = h->variant == 2 ? 0xFFFFu : h->acc_mask;   // variant 2: no pruning at any size
+  p.n_row_entries = h->n_row_entries;
+  p.n_row_entries_shift = h->n_row_entries_shift;
+  p.acc_mask_shift = h->variant == 2 ? 0xFFFFu : h->acc_mask_shift;
+  p.cfar_on = h->cfar_on ? 1 : 0;
+}
+
 int crn_sense_kernel_info(crn_handle *h, char *name, int32_t name_len, int32_t *threads_per_block,
                           int32_t *lds_bytes, int32_t *epochs_per_block) {
   if (!h) return crn::fail(CRN_ERR_ARG, "null handle");
   std::lock_guard<std::mutex> lk(h->tables_mu);
-  int thr = 0, lds = 0, epb = 0;
-  crn::sense_geometry(h->cfg.fft_len, h->variant, &thr, &lds, &epb);
-  if (threads_per_block) *threads_per_block = thr;
-  if (lds_bytes) *lds_bytes = lds;
-  if (epochs_per_block) *epochs_per_block = epb;
-  if (name && name_len > 0) {
-    int nbuf = 1, pf = 0, nt = 0, tl = 0, pk = 0;
-    crn::sense_variant(h->cfg.fft_len, h->cfg.mode == CRN_MODE_REF_MAG || h->cfg.window != CRN_WINDOW_RECT ? -1 : h->variant,
-                       &nbuf, &pf, &nt, &tl, &pk);
-    const bool plain4096 = h->cfg.fft_len == 4096 && h->cfg.mode != CRN_MODE_REF_MAG && h->cfg.window == CRN_WINDOW_RECT;
-    // what a launch without a spectrum output runs (a spectrum request falls back to full rows / the LDS close)
-    // (the plain 4096-point kernel labels its register rows 7 bins early — crn_kernels.h, bin_of — and is judged by the plan cut at those rows)
-    const int n_rows_ent = plain4096 ? h->n_row_entries_shift : h->n_row_entries;
-    const unsigned plan_mask = plain4096 ? h->acc_mask_shift : h->acc_mask;
-    bool reg_close = n_rows_ent > 0 && h->cfg.window == CRN_WINDOW_RECT;
-    if (plain4096) {  // the forms of the plain kernel that carry the register close
-      const int v = h->variant == 0 ? 13 : h->variant;
-      const bool rows_ok = (plan_mask & ~0x8267u) == 0;
-      reg_close = reg_close && (v == 2 || v == 13 || v == 17 || (v == 7 && rows_ok));
-    }
-    // pass 3 / accumulate pruned to the reference channel plan's registers: the plain 4096-point kernel's default form, and the
-    // register-close kernels of every other size and mode (what a launch without a spectrum output runs)
-    const unsigned ref_mask = crn::sense_ref_acc_mask(h->cfg.fft_len);
-    const bool inside = (plan_mask & ~ref_mask) == 0 && ref_mask != 0xFFFFu && h->variant != 2;   // (N = 4096: the same seven rows in both labellings)
-    const bool pruned = reg_close && inside && h->cfg.window == CRN_WINDOW_RECT && (!plain4096 || h->variant == 0 || h->variant == 13);
-    // periodic Hann in energy mode: the window is folded into pass 1 (whole frames); with the Welch scan's plan
-    // (N = 4096, equal contiguous bands) the close forms band sums by DPP
-    const bool hann_fold = h->cfg.window == CRN_WINDOW_HANN && h->cfg.mode != CRN_MODE_REF_MAG;
-    const bool aligned = hann_fold && h->cfg.fft_len == 4096 && h->aligned_shift != 0;
-    if (hann_fold) tl = 1;
-    char prune_note[64] = "";
-    if (pruned) std::snprintf(prune_note, sizeof(prune_note), ",PASS3_ROWS=%d-of-16(reference channel plan)", __builtin_popcount(ref_mask));
-    std::snprintf(name, (size_t)name_len, "sense_kernel<R3=%d,NBUF=%d,PREFETCH=%d,NT=%d,TW2LDS=%d,PK=%d,MAG=%d,WIN=%s,CLOSE=%s%s>",
-                  h->cfg.fft_len / 256, nbuf, pf, nt, tl, pk,
-                  h->cfg.mode == CRN_MODE_REF_MAG, h->cfg.window == CRN_WINDOW_RECT ? "0" : hann_fold ? "hann-in-pass1" : "table",
-                  h->cfar_on ? "lds+cfar" : aligned ? "aligned-bands(dpp)" : reg_close ? "registers" : "lds",
-                  h->cfar_on ? "" : prune_note);
-  }
+  // the form a streaming launch of whole frames without a spectrum output runs (a spectrum request falls back to full rows / the LDS close)
+  crn::SenseParams p{};
+  p.L = h->cfg.fft_len;
+  fill_plan_facts(h, false, p);
+  const std::optional<crn::FormKey> k = crn::select_form(
+      crn::make_form_query(p, h->cfg.fft_len, h->cfg.mode == CRN_MODE_REF_MAG, h->cfg.window != CRN_WINDOW_RECT, h->variant, false));
+  if (!k) return crn::fail(CRN_ERR_STATE, "no kernel form for this handle");
+  const crn::FormGeometry g = crn::form_geometry(*k);
+  if (threads_per_block) *threads_per_block = g.threads;
+  if (lds_bytes) *lds_bytes = g.lds_bytes;
+  if (epochs_per_block) *epochs_per_block = g.epochs_per_block;
+  if (name && name_len > 0) crn::form_name(*k, name, (size_t)name_len);
   return CRN_OK;
 }
 
@@ -371,17 +356,12 @@ static int run_device_impl(crn_handle *h, const void *d_iq, int64_t n_epochs, in
   p.n_bands = c.n_bands;
   p.decide = c.decide;
   p.ref_band = c.ref_band;
-  p.hann_sym = c.window == CRN_WINDOW_HANN;
-  p.aligned_shift = d_out->spectrum == nullptr ? h->aligned_shift : 0;
-  p.acc_mask = h->variant == 2 ? 0xFFFFu : h->acc_mask;   // variant 2: no pruning at any size
+  fill_plan_facts(h, d_out->spectrum != nullptr, p);
   {  // 1 / full scale for a sum of magnitudes, its square for energies (2^-15 / 2^-30 by default: exact)
     const double u = 1.0 / h->wire_full_scale;
     p.wire_unscale = (float)(c.mode == CRN_MODE_REF_MAG ? u : u * u);
   }
-  p.n_row_entries = h->n_row_entries;
   p.row_entries_shift = h->d_row_entries_shift;
-  p.n_row_entries_shift = h->n_row_entries_shift;
-  p.acc_mask_shift = h->variant == 2 ? 0xFFFFu : h->acc_mask_shift;
   p.features = d_out->features;
   // (a measurement form that writes time stamps puts them there: libcrnsense_ab.so only)
   p.ann_out = (c.decide == CRN_DECIDE_ANN || crn::sense_variant_traces(h->variant)) ? d_out->ann_out : nullptr;
@@ -389,7 +369,6 @@ static int run_device_impl(crn_handle *h, const void *d_iq, int64_t n_epochs, in
   p.occupancy = d_out->occupancy;
   p.spectrum = d_out->spectrum;
   if (h->cfar_on) {
-    p.cfar_on = 1;
     p.cfar_guard = h->cfar.guard;
     p.cfar_train = h->cfar.train;
     p.cfar_min_bins = h->cfar.min_bins;

@@ -6,6 +6,8 @@
 #include <type_traits>
 #include <stdint.h>
 
+#include "crn_forms.h"
+
 namespace crn {
 
 // A complex fp32 value lives in an even-aligned VGPR pair (re, im) so the packed-f32 VALU forms
@@ -249,27 +251,7 @@ CRN_HD void dft16_hann(const cx (&in)[16], cx (&out)[16], const cx (&wp)[4], con
   dft16_level_b<PK>(y, out, hook);
 }
 
-// The reference hard-codes its channel plan (bins 0-15 + 496-510, 55-84, 189-221, 300-309 of 512:
-// CE_Predictive_Node.cpp:173-191).  At N = 4096 those bands touch 7 of the 16 blocks of 256 bins, and
-// the last radix-4 level of pass 3 produces exactly one block per output: row d = bins
-// [256 d, 256 d + 256).  For band tables inside these rows, and when no per-bin spectrum is asked
-// for, pass 3 forms and accumulates only the needed outputs (bit-identical for those bins).
-static constexpr unsigned kRefPlanRows = 0x8267u;  // rows {0, 1, 2, 5, 6, 9, 15}
-
-// The same at every size.  After pass 3 thread (a, g) holds bin a + 16 (g J + j) + 256 d in accumulator register j R3 + d
-// (J = 16 / R3, N = 256 R3): which of the 16 registers can hold a bin of the reference's channel plan scaled to N points — bit
-// j R3 + d.  N = 4096: the rows above (J = 1: register = row), 7 of 16; N = 512: 7; N = 1024: 12; N = 2048: 11.  Band tables inside
-// the mask, with no per-bin spectrum asked for, run kernels whose pass 3 forms and accumulates only those registers.
-constexpr unsigned ref_acc_mask(int R3) {
-  const int seg[5][2] = {{0, 16}, {496, 511}, {55, 85}, {189, 222}, {300, 310}};   // CE_Predictive_Node.cpp:173-191, of 512 bins
-  const int J = 16 / R3, S = R3 / 2;                                               // N / 512
-  unsigned mask = 0;
-  for (int s = 0; s < 5; s++)
-    for (int k = seg[s][0] * S; k < seg[s][1] * S; k++) mask |= 1u << ((((k & 255) >> 4) % J) * R3 + (k >> 8));
-  return mask;
-}
-static_assert(ref_acc_mask(16) == kRefPlanRows, "N = 4096: register = 256-bin row");
-
+// (which outputs the reference channel plan needs — kRefPlanRows, ref_acc_mask — is stated in crn_forms.h)
 // DFT16 whose last level only forms the outputs named in MASK (bit d = X[d] needed).
 template <bool PK, unsigned MASK>
 CRN_HD void dft16_pruned(const cx (&in)[16], cx (&out)[16]) {

@@ -27,9 +27,7 @@ namespace crn {
 // Epoch close (reference .cpp:157-261 + the reset at :287-288): K-frame averages -> LDS in natural
 // bin order -> band sums -> features -> decision.  Resets the accumulators for the next epoch.
 // ---------------------------------------------------------------------------------------------
-// LDS behind the exchange buffers and the tw2 table, used by the epoch close: the band table copy,
-// then [8 teams][16] per-team band partials of the register path.
-constexpr int kCloseLdsBytes = kBandTabWords * 4 + 8 * 16 * 4;
+// (LDS behind the exchange buffers and the tw2 table, used by the epoch close: kCloseLdsBytes, crn_forms.h)
 
 // LDS address-space views for the epoch close (see epoch_close): ds_* instructions, lgkmcnt only.
 typedef __attribute__((address_space(3))) float lds_f32;

@@ -3,7 +3,7 @@
 #ifndef CRN_FRAME_H
 #define CRN_FRAME_H
 #include "crn_butterflies.h"
-#include "crn_kernels.h"
+#include "crn_forms.h"
 
 namespace crn {
 // ---------------------------------------------------------------------------------------------
@@ -113,27 +113,9 @@ CRN_DEV void wave_sync() {
 //   OCC      workgroups per CU the register allocation must allow
 //   FULL     every frame brings all N samples (L == N): no zero-padding mask
 //   PK       packed-f32 butterflies (see M<PK>)
+//   OPT      OR of the flags of crn_forms.h (kSpread .. kCfar)
+// Which combinations are compiled, and which one a launch runs: crn_forms.h, the one place that lists them.
 // ---------------------------------------------------------------------------------------------
-// OPT flags (the measurement build adds kTrace: crn_frame_ab.h)
-enum : int {
-  kSpread = 4,   // next frame's loads issued from inside passes 1 and 2, one per radix-4 group
-  kLdsBlk = 32,  // LDS reads as hand-written ds_read_b64 blocks (no ds_read2_b64 merging)
-  kTw1C = 64,    // pass-1 twiddles stored compressed (9 instead of 15 complex values)
-  kRows = 256,   // pass 3 and the accumulate limited to the registers that can hold a bin of the reference channel plan (ref_acc_mask)
-  kMulti = 512,  // a workgroup streams through several consecutive epoch groups
-  kPrioValu = 1024, // s_setprio 1 through the butterflies of passes 1 and 2 (where the prefetch loads issue)
-  kRegBands = 8192, // epoch close forms the band sums from registers (plans with n_row_entries > 0, no spectrum)
-  kHannSym = 16384, // periodic Hann folded into pass 1's first butterflies (w[n + N/2] = 1 - w[n]): 8 window registers
-  kTw2Early = 32768, // TW2LDS: the first block of pass-2 twiddles is read from LDS before the butterflies that precede its use
-  kAlignedBands = 65536, // N = 4096, equal contiguous bands of 64 / 128 / 256 bins (p.aligned_shift): band sums by DPP + one barrier
-  kSc16 = 131072,   // samples in HBM are the radio's wire format (two int16 per complex sample, 4 bytes): converted in pass 1
-                    // (instantiated by crn_kernels_sc16.hip: a library built with make SC16=1)
-  kDeal = 1048576,  // sense_kernel_dealt (launches of a few epochs): one epoch per workgroup, its frames dealt to the lane groups; pass 3
-                    // parks each frame's per-bin values in LDS (ph_pass3_park) and the accumulate is replayed in frame order afterwards
-  kCfar = 2097152,  // per-bin CA-CFAR on the LDS spectrum image after the band sums (crn_sense_set_cfar): bit mask, per-band counts and
-                    // the decision in place of the threshold rule (epoch_close, LDS form only)
-};
-
 template <int R3_, int NBUF_, bool PREFETCH_, bool NT_, bool MAG_, bool WIN_, bool TW2LDS_, int OCC_, bool FULL_, bool PK_, int OPT_ = 0>
 struct Cfg {
   static constexpr int OPT = OPT_;  // OR of the flags above
@@ -153,21 +135,6 @@ struct BinMap {
   CRN_DEV constexpr int q(int a, int m_lo, int j) { return lane_coord<S>(a, m_lo, j, Geo<C::R3>::J); }   // register row j R3 + .: its offset in a 256-bin row
   CRN_DEV constexpr int bin(int a, int m_lo, int j, int d) { return bin_of<S>(q(a, m_lo, j), d, Geo<C::R3>::N); }
 };
-// The reference channel plan's registers under that map: ref_acc_mask with every bin moved up by S.
-constexpr unsigned ref_acc_mask_shifted(int R3, int S) {
-  const int seg[5][2] = {{0, 16}, {496, 511}, {55, 85}, {189, 222}, {300, 310}};   // as in ref_acc_mask (crn_butterflies.h)
-  const int J = 16 / R3, Sc = R3 / 2, N = 256 * R3;
-  unsigned mask = 0;
-  for (int s = 0; s < 5; s++)
-    for (int k = seg[s][0] * Sc; k < seg[s][1] * Sc; k++) {
-      const int ks = (k + S) & (N - 1);
-      mask |= 1u << ((((ks & 255) >> 4) % J) * R3 + (ks >> 8));
-    }
-  return mask;
-}
-static_assert(ref_acc_mask_shifted(16, 0) == kRefPlanRows && ref_acc_mask_shifted(2, 0) == ref_acc_mask(2), "S = 0: ref_acc_mask itself");
-static_assert(ref_acc_mask_shifted(16, kTw1cRowShift) == kRefPlanRows, "N = 4096: the plan reaches the same seven rows when they start 7 bins early");
-
 // Per-thread state that lives across the frames of an epoch.
 template <class C>
 struct FrameCtx {

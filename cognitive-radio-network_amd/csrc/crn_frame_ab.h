@@ -1,6 +1,6 @@
 // crn_frame_ab.h — MEASUREMENT BUILD ONLY (libcrnsense_ab.so, -DCRN_AB_VARIANTS; included by crn_epoch_close.h).  What the shipped
-// library does not carry: the kTrace flag and the in-kernel time stamps of variant 17 (tools/gpu_wg_placement.py).  Every other
-// measurement variant that is still compiled (7, 19-22, 26, 27: crn_dispatch_ab.h) is a combination of the shipped flags.  The schedules,
+// library does not carry: the in-kernel time stamps of variant 17 (the kTrace flag of crn_forms.h; tools/gpu_wg_placement.py).  Every other
+// measurement variant that is still compiled (7, 19-22, 26, 27: crn_forms.h) is a combination of the shipped flags.  The schedules,
 // ablations and layouts that were measured and not kept in rounds 1-4 (variants 1, 3-6, 8-12, 14-16, 18, 24, 25) were deleted in
 // round 5: docs/history/removed_variants.md names the commit that last held them.
 #ifndef CRN_FRAME_AB_H
@@ -8,10 +8,6 @@
 #include "crn_frame.h"
 
 namespace crn {
-enum : int {
-  kTrace = 4096,   // s_memtime / s_memrealtime stamps of the workgroup start and the epoch close, written over the ann_out buffer
-};
-
 template <class C>
 struct CloseTrace {
   static constexpr bool ON = (C::OPT & kTrace) != 0;

@@ -22,141 +22,20 @@
 
 namespace crn {
 
-// Kernel forms selectable through crn_sense_set_variant (0 = default).  The shipped library (libcrnsense.so) compiles the two that are
-// forms of the product — 13 (= 0, the default) and 2 (no pass-3 row pruning: what any band table outside the reference plan's rows runs
-// anyway) — and refuses every other number.  libcrnsense_ab.so (-DCRN_AB_VARIANTS; tools/ and the A/B test) adds measurement forms:
-// crn_dispatch_ab.h, the one seam in this file.  The numbers are the ones profiles/ and docs/history/ quote; the schedules, ablations
-// and layouts of rounds 1-4 that were measured and not kept are gone from the tree (docs/history/removed_variants.md).
-static constexpr int kNumVariants = 27, kDefaultVariant = 13;
-#ifdef CRN_AB_VARIANTS
-#include "crn_dispatch_ab.h"
-#else
-static bool measurement_variant(int) { return false; }           // no measurement forms in this build
-static bool measurement_variant_traces(int) { return false; }
-static void measurement_variant_desc(int, int *, int *) {}
-template <int R3>
-static bool launch_measurement_form(const SenseParams &, bool, bool, int, hipStream_t, hipError_t *) { return false; }
-#endif
-
-// Does this build of the library carry variant v?  (0 = default.)
-bool sense_variant_available(int v) { return v == 0 || v == kDefaultVariant || v == 2 || measurement_variant(v); }
-// ... and does it write time stamps over the ann_out buffer (so that the buffer must reach the kernel whatever the decision rule)?
-bool sense_variant_traces(int v) { return measurement_variant_traces(v); }
-
 // Wire-format input: crn_kernels_sc16.hip, linked only into a library built with `make SC16=1` (a weak reference: null when absent).
 __attribute__((weak)) hipError_t launch_sense_sc16(const SenseParams &p, int fft_len, bool mag, bool win, int variant, hipStream_t stream, int *deal_rounds_run);
 
-// A handle with CFAR on (crn_sense_set_cfar; energy mode, float samples): the frame loop of the form the same handle runs with CFAR off
-// — so that the spectrum and the features are the same bits — closed through the LDS walk with the CFAR pass (crn_epoch_close.h).
-// No register-band, pruned-row, aligned-band or dealt forms.  The windowed forms below 4096 points take two workgroups per CU: at
-// three their frame loop spills (as the CFAR-off forms do), and a scratch reload in the loop waits behind the prefetch.
-template <int R3>
-static hipError_t launch_cfar(const SenseParams &p, bool win, hipStream_t stream) {
-  constexpr int kBase = kSpread | kLdsBlk | kPrioValu | kMulti | kCfar;
-  constexpr int kWinOcc = R3 == 16 ? 3 : 2;
-  if (win && p.hann_sym && p.L == Geo<R3>::N)
-    return launch_cfg<Cfg<R3, 1, true, true, false, true, true, kWinOcc, true, true, kBase | kHannSym | kTw2Early>>(p, stream);
-  if (win) return launch_cfg<Cfg<R3, 1, true, true, false, true, true, kWinOcc, false, true, kBase>>(p, stream);
-  if constexpr (R3 == 16) {
-    if (p.L == Geo<R3>::N) return launch_cfg<Cfg<R3, 1, true, true, false, false, true, 4, true, true, kBase | kTw1C>>(p, stream);
-  }
-  return launch_cfg<Cfg<R3, 1, true, true, false, false, false, 3, false, true, kBase>>(p, stream);
-}
-
-// The forms other than the default exist for N = 4096 only; other sizes always run the default.
-template <int R3>
-static hipError_t launch_r(const SenseParams &p, bool mag, bool win, int variant, hipStream_t stream, int *deal_rounds_run) {
-  if (p.cfar_on) return mag ? hipErrorInvalidValue : launch_cfar<R3>(p, win, stream);
-  constexpr int kBase = kSpread | kLdsBlk | kPrioValu | kMulti;
-  if constexpr (R3 <= 4) {   // a launch of a few epochs (crn_api.cpp sets deal_rounds): one epoch per workgroup, frames dealt to its lane groups
-    if (p.deal_rounds > 0) {
-      const hipError_t e = win ? launch_dealt_win<R3, 0>(p, stream) : launch_dealt<R3, 0>(p, mag, stream);
-      if (e != hipErrorLaunchOutOfResources) {
-        if (e == hipSuccess && deal_rounds_run) *deal_rounds_run = p.deal_rounds;
-        return e;
-      }
-      SenseParams q = p;   // the device refused the LDS the frame slots need (crn_sense_kernel.h: launch_dealt_cfg): the streaming form takes it
-      q.deal_rounds = 0;
-      return launch_r<R3>(q, mag, win, variant, stream, deal_rounds_run);
-    }
-  }
-  if (hipError_t e; launch_measurement_form<R3>(p, mag, win, variant, stream, &e)) return e;   // (libcrnsense_ab.so only)
-  // Periodic Hann (the Welch configuration), whole frames, energy mode: the window rides in pass 1's first
-  // butterflies and the first block of pass-2 twiddles is read ahead of its use (+1 % on the Welch stream, and 8
-  // window registers fewer; the A/B numbers are in docs/history/DESIGN_r03.md §5)
-  // (a windowed handle runs this whatever plain-kernel form it selects)
-  if (win && !mag && p.hann_sym && p.L == Geo<R3>::N) {
-    if constexpr (R3 == 16) {  // the Welch scan's plan (equal contiguous bands): band sums without the spectrum image
-      if (p.aligned_shift != 0)
-        return launch_cfg<Cfg<R3, 1, true, true, false, true, true, 3, true, true, kBase | kHannSym | kTw2Early | kAlignedBands>>(p, stream);
-    }
-    return launch_cfg<Cfg<R3, 1, true, true, false, true, true, 3, true, true, kBase | kHannSym | kTw2Early>>(p, stream);
-  }
-  // The plain 4096-point kernel runs 4 workgroups per CU with the compressed pass-1 table and pass 2
-  // from LDS; everything else 3 per CU (windowed kernels carry 16 more registers: the window).
-  // 3 workgroups per CU, all 30 twiddles in registers at N < 4096 (4 per CU with the compressed tables was
-  // measured at these sizes: equal at 1024, -3 % at 512, -7 % at 2048), streaming workgroups
-  // (+2.5-3 % everywhere; N = 1024 used to spill with them until the epoch close was slimmed).
-  // Windowed kernels (16 window registers, and for Welch three half-frame sets) read the pass-2
-  // twiddles from LDS at every size: in registers they spill inside the frame loop.
-  if (win) return launch_default<R3, 1, true, true, true, 3, true, kBase, 2>(p, mag, win, stream);
-  if (R3 != 16 || mag || p.L != Geo<R3>::N) return launch_default<R3, 1, true, true, false, 3, true, kBase, 1, true, R3 != 16>(p, mag, win, stream);
-  if constexpr (R3 == 16) {
-    constexpr int kPlain = kSpread | kLdsBlk | kTw1C | kMulti | kPrioValu;
-    // (kTw1C: these kernels' register rows start 7 bins early — BinMap — so the plan is judged by the entries and the mask cut at those rows)
-    const bool regb = reg_bands_shift(p);
-    if (variant != 2 && ref_plan_rows_shift(p))   // the reference channel plan's rows only (the default, 13)
-      return launch_rn<R3, 1, true, true, true, 4, true, kPlain | kRows | kRegBands>(p, mag, win, stream);
-    // another plan, a per-bin spectrum request, or variant 2: no pruning
-    if (regb) return launch_rn<R3, 1, true, true, true, 4, true, kPlain | kRegBands>(p, mag, win, stream);
-    return launch_rn<R3, 1, true, true, true, 4, true, kPlain>(p, mag, win, stream);
-  }
-  return hipErrorInvalidValue;
-}
+// This unit's kernels: the float-sample forms (crn_forms.h; with -DCRN_AB_VARIANTS the measurement forms too).
+struct FloatUnit {
+  static constexpr size_t n = kNumFloatForms;
+  static constexpr FormKey row(size_t i) { return kFloatForms.row[i]; }
+};
 
 hipError_t launch_sense(const SenseParams &p, int fft_len, bool mag, bool win, int variant,
                         hipStream_t stream, bool sc16, int *deal_rounds_run) {
   if (deal_rounds_run) *deal_rounds_run = 0;
   if (sc16) return launch_sense_sc16 ? launch_sense_sc16(p, fft_len, mag, win, variant, stream, deal_rounds_run) : hipErrorNotSupported;
-  switch (fft_len) {
-    case 512: return launch_r<2>(p, mag, win, variant, stream, deal_rounds_run);
-    case 1024: return launch_r<4>(p, mag, win, variant, stream, deal_rounds_run);
-    case 2048: return launch_r<8>(p, mag, win, variant, stream, deal_rounds_run);
-    case 4096: return launch_r<16>(p, mag, win, variant, stream, deal_rounds_run);
-    default: return hipErrorInvalidValue;
-  }
-}
-
-int sense_num_variants() { return kNumVariants; }
-
-int sense_deal_rounds(int fft_len, bool mag, bool win, bool hann_whole_frames, int K, size_t lds_budget) {
-  if (fft_len != 512 && fft_len != 1024) return 0;
-  if (win && (mag || !hann_whole_frames)) return 0;   // the one windowed dealt form: periodic Hann, energy mode, whole frames
-  const int r3 = fft_len / 256, t = 16 * r3, groups = 256 / t;
-  if (K < 2) return 0;   // one frame: nothing to deal
-  const int rounds = (K + groups - 1) / groups;
-  const size_t lds = ((size_t)groups * 16 * (t + r3) + 16 * r3) * sizeof(cx) + kCloseLdsBytes + (size_t)rounds * groups * fft_len * (mag ? 4 : 8);
-  return lds <= lds_budget ? rounds : 0;
-}
-unsigned sense_ref_acc_mask(int fft_len) { return ref_acc_mask(fft_len / 256); }
-
-void sense_variant(int fft_len, int variant, int *nbuf, int *prefetch, int *nt, int *tw2lds, int *pk) {
-  *nbuf = 1; *prefetch = 1; *nt = 1; *pk = 1;
-  *tw2lds = (variant >= 0 && fft_len == 4096) ? 1 : 0;   // the plain 4096-point kernel reads its pass-2 twiddles from LDS (the other
-                                                         // sizes' plain kernels keep them in registers; windowed kernels: crn_api.cpp)
-  if (fft_len == 4096 && measurement_variant(variant)) measurement_variant_desc(variant, nbuf, tw2lds);
-}
-
-void sense_geometry(int fft_len, int variant, int *threads, int *lds_bytes, int *epochs_per_block) {
-  const int r3 = fft_len / 256;
-  const int t = 16 * r3;
-  const int groups = 256 / t;
-  int nbuf, pf, nt, tl, pk;
-  sense_variant(fft_len, variant, &nbuf, &pf, &nt, &tl, &pk);
-  *threads = 256;
-  *epochs_per_block = groups;
-  (void)tl;
-  *lds_bytes = (groups * nbuf * 16 * (t + r3) + 16 * r3) * 8 + kCloseLdsBytes;
+  return launch_selected<FloatUnit>(p, make_form_query(p, fft_len, mag, win, variant, false), stream, deal_rounds_run);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -5,51 +5,14 @@
 
 namespace crn {
 
-// Wire-format input (kSc16): the default kernels of every size, mode and window, the plain 4096-point kernel's three forms, and the
-// Welch configuration's kernel (periodic Hann, whole frames, energy).
-template <int R3>
-static hipError_t launch_r_sc16(const SenseParams &p, bool mag, bool win, int variant, hipStream_t stream, int *deal_rounds_run) {
-  constexpr int kBase = kSpread | kLdsBlk | kPrioValu | kMulti | kSc16;
-  if constexpr (R3 <= 4) {   // a launch of a few epochs: frames dealt to the workgroup's lane groups (sense_kernel_dealt)
-    if (p.deal_rounds > 0) {
-      const hipError_t e = win ? launch_dealt_win<R3, kSc16>(p, stream) : launch_dealt<R3, kSc16>(p, mag, stream);
-      if (e != hipErrorLaunchOutOfResources) {
-        if (e == hipSuccess && deal_rounds_run) *deal_rounds_run = p.deal_rounds;
-        return e;
-      }
-      SenseParams q = p;   // (the device refused the LDS the frame slots need: the streaming form)
-      q.deal_rounds = 0;
-      return launch_r_sc16<R3>(q, mag, win, variant, stream, deal_rounds_run);
-    }
-  }
-  if (win) {
-    // everything that is not the Welch configuration's kernel: the generic windowed kernels (window table in registers)
-    if (mag || !p.hann_sym || p.L != Geo<R3>::N) return launch_default<R3, 1, true, true, true, 3, true, kBase, 2, false>(p, mag, win, stream);
-    if constexpr (R3 == 16) {
-      if (p.aligned_shift != 0)
-        return launch_cfg<Cfg<R3, 1, true, true, false, true, true, 3, true, true, kBase | kHannSym | kTw2Early | kAlignedBands>>(p, stream);
-    }
-    return launch_cfg<Cfg<R3, 1, true, true, false, true, true, 3, true, true, kBase | kHannSym | kTw2Early>>(p, stream);
-  }
-  if constexpr (R3 == 16) {
-    if (!mag && p.L == Geo<R3>::N) {
-      if (ref_plan_rows_shift(p))   // (the kTw1C kernels' own rows: crn_sense_kernel.h)
-        return launch_rn<R3, 1, true, true, true, 4, true, kBase | kTw1C | kRows | kRegBands>(p, mag, win, stream);
-      if (reg_bands_shift(p)) return launch_rn<R3, 1, true, true, true, 4, true, kBase | kTw1C | kRegBands>(p, mag, win, stream);
-      return launch_rn<R3, 1, true, true, true, 4, true, kBase | kTw1C>(p, mag, win, stream);
-    }
-  }
-  return launch_default<R3, 1, true, true, false, 3, true, kBase, 1, false, R3 != 16>(p, mag, win, stream);   // (no plan-specific pruning in wire format)
-}
+// This unit's kernels: the wire-format forms (crn_forms.h: every row carries kSc16).
+struct WireUnit {
+  static constexpr size_t n = kNumWireForms;
+  static constexpr FormKey row(size_t i) { return kWireForms.row[i]; }
+};
 
 hipError_t launch_sense_sc16(const SenseParams &p, int fft_len, bool mag, bool win, int variant, hipStream_t stream, int *deal_rounds_run) {
-  switch (fft_len) {
-    case 512: return launch_r_sc16<2>(p, mag, win, variant, stream, deal_rounds_run);
-    case 1024: return launch_r_sc16<4>(p, mag, win, variant, stream, deal_rounds_run);
-    case 2048: return launch_r_sc16<8>(p, mag, win, variant, stream, deal_rounds_run);
-    case 4096: return launch_r_sc16<16>(p, mag, win, variant, stream, deal_rounds_run);
-    default: return hipErrorInvalidValue;
-  }
+  return launch_selected<WireUnit>(p, make_form_query(p, fft_len, mag, win, variant, true), stream, deal_rounds_run);
 }
 
 // complex floats -> the radio's wire format (int16 pairs, full scale 32768): crn_pack_sc16_device

@@ -2,6 +2,7 @@
 #ifndef CRN_SENSE_KERNEL_H
 #define CRN_SENSE_KERNEL_H
 #include <atomic>
+#include <utility>
 
 #include "crn_epoch_close.h"
 
@@ -376,45 +377,6 @@ static hipError_t launch_dealt_cfg(const SenseParams &p, hipStream_t stream) {
   return hipGetLastError();
 }
 
-// The windowed dealt-frame form: periodic Hann on whole frames in energy mode, riding in pass 1's first butterflies (kHannSym) exactly as
-// the streaming dispatch picks it for the same launch, so that the arithmetic is the same bit for bit — what the engine's `-m welch` /
-// `-m scan` launch.  (Other windows and |X| mode have no dealt form: sense_deal_rounds says 0 and the streaming kernel takes the launch.)
-// Windowed kernels close through the LDS walk.
-template <int R3, int OPT>
-static hipError_t launch_dealt_win(const SenseParams &p, hipStream_t stream) {
-  constexpr int kO = kSpread | kLdsBlk | kDeal | OPT;
-  return launch_dealt_cfg<Cfg<R3, 1, true, false, false, true, false, 1, false, true, kO | kHannSym>>(p, stream);
-}
-
-// The register form of the epoch close applies to band plans the host could cut into row entries
-// (crn_tables.cpp) when no per-bin spectrum is stored.
-static bool reg_bands(const SenseParams &p) { return p.n_row_entries > 0 && p.spectrum == nullptr; }
-// The same two questions for the kTw1C kernels (the plain 4096-point forms), whose register rows start kTw1cRowShift bins early: the
-// entries cut at those rows, and the reference plan's rows among them (ref_acc_mask_shifted: the same seven).
-static bool reg_bands_shift(const SenseParams &p) { return p.n_row_entries_shift > 0 && p.spectrum == nullptr; }
-static bool ref_plan_rows_shift(const SenseParams &p) { return reg_bands_shift(p) && (p.acc_mask_shift & ~ref_acc_mask_shifted(16, kTw1cRowShift)) == 0; }
-// ... and pass 3 / the accumulate keep only the reference channel plan's registers when every band bin sits in one of them.
-template <int R3>
-static bool ref_plan_rows(const SenseParams &p) { return reg_bands(p) && ref_acc_mask(R3) != 0xFFFFu && (p.acc_mask & ~ref_acc_mask(R3)) == 0; }
-// Which close a launch gets is ONE rule for the streaming and the dealt-frame kernels (their outputs are bit-identical because they sum
-// in the same order): the register close for |X| mode, and for energy mode on whole frames or on the reference plan; the LDS walk
-// otherwise (energy mode, short packets, another small plan; every plan too big for row entries; every spectrum request).
-template <int R3>
-static bool register_close(const SenseParams &p, bool mag) { return reg_bands(p) && (mag || p.L == Geo<R3>::N || ref_plan_rows<R3>(p)); }
-
-// Dealt-frame forms of a size: |X| or energy, band sums from registers or through the LDS walk; short frames are masked at run time.
-template <int R3, int OPT>
-static hipError_t launch_dealt(const SenseParams &p, bool mag, hipStream_t stream) {
-  constexpr int kO = kSpread | kLdsBlk | kDeal | OPT;
-  const bool regb = register_close<R3>(p, mag);
-  if (mag) {
-    if (regb) return launch_dealt_cfg<Cfg<R3, 1, true, false, true, false, false, 1, false, true, kO | kRegBands>>(p, stream);
-    return launch_dealt_cfg<Cfg<R3, 1, true, false, true, false, false, 1, false, true, kO>>(p, stream);
-  }
-  if (regb) return launch_dealt_cfg<Cfg<R3, 1, true, false, false, false, false, 1, false, true, kO | kRegBands>>(p, stream);
-  return launch_dealt_cfg<Cfg<R3, 1, true, false, false, false, false, 1, false, true, kO>>(p, stream);
-}
-
 // ---------------------------------------------------------------------------------------------
 // launch dispatch
 // ---------------------------------------------------------------------------------------------
@@ -451,55 +413,45 @@ static hipError_t launch_cfg(const SenseParams &p, hipStream_t stream) {
   return hipGetLastError();
 }
 
-// The forms every size has, by mode / window / packet length / close.  What is specialised is what BASELINE.json's configurations and
-// the engine run: whole frames (FULL: no zero-padding mask) where the band plan is the reference's (kRows | kRegBands) or a small one in
-// energy mode (kRegBands); everything else — table windows, |X| mode with another plan or a spectrum request, short packets with a
-// small custom plan — runs ONE form that masks at run time (and closes through the LDS walk where the register close has no form).
-//   WHICH        0 all, 1 unwindowed kernels only, 2 windowed only
-//   PRUNE        the reference-plan forms exist (not in the wire-format unit)
-//   ENERGY_FULL  the unwindowed energy-mode whole-frame forms belong to this call (false at N = 4096: launch_rn has them)
-template <int R3, int NBUF, bool PREFETCH, bool NT, bool TW2LDS, int OCC, bool PK, int OPT = kSpread | kLdsBlk | kPrioValu | kMulti,
-          int WHICH = 0, bool PRUNE = true, bool ENERGY_FULL = true>
-static hipError_t launch_default(const SenseParams &p, bool mag, bool win, hipStream_t stream) {
-  const bool full = p.L == Geo<R3>::N;
-  const bool regb = register_close<R3>(p, mag);  // small band plan, no spectrum: band sums from registers (see register_close)
-  // ... and when every band bin sits in a register the reference channel plan also uses (ref_acc_mask), pass 3 and the accumulate
-  // keep only those registers: 7 of 16 at N = 512 (where the reference's |X| costs a square root per bin and frame), 12 / 11 / 7 at
-  // 1024 / 2048 / 4096
-  [[maybe_unused]] const bool prune = PRUNE && ref_plan_rows<R3>(p);
-#define CRN_GO(MAGV, WINV, FULLV, EXTRA) return launch_cfg<Cfg<R3, NBUF, PREFETCH, NT, MAGV, WINV, TW2LDS, OCC, FULLV, PK, OPT | (EXTRA)>>(p, stream)
-  if constexpr (WHICH != 1) {   // table windows: one form per mode
-    if (win) { if (mag) CRN_GO(true, true, false, 0); else CRN_GO(false, true, false, 0); }
-  }
-  if constexpr (WHICH != 2) {
-    if constexpr (PRUNE) {      // the reference channel plan: |X| and energy, whole frames and short packets
-      if (prune) {
-        if (mag) { if (full) CRN_GO(true, false, true, kRegBands | kRows); else CRN_GO(true, false, false, kRegBands | kRows); }
-        if constexpr (ENERGY_FULL) { if (full) CRN_GO(false, false, true, kRegBands | kRows); }
-        if (!full) CRN_GO(false, false, false, kRegBands | kRows);
-      }
-    }
-    if (regb) {                 // another small plan: register close for |X| (any packet length) and for energy on whole frames
-      if (mag) CRN_GO(true, false, false, kRegBands);
-      if constexpr (ENERGY_FULL) { if (full) CRN_GO(false, false, true, kRegBands); }
-      // (a unit without the reference-plan forms — the wire-format one — closes that plan's short packets from registers all the same:
-      // the same sums in the same order as the float path's pruned form)
-      if constexpr (!PRUNE) { if (!full) CRN_GO(false, false, false, kRegBands); }
-    }
-    if (mag) CRN_GO(true, false, false, 0);   // any plan, spectrum requests: the LDS walk
-    if constexpr (ENERGY_FULL) { if (full) CRN_GO(false, false, true, 0); }
-    if (!full) CRN_GO(false, false, false, 0);
-  }
-  return hipErrorInvalidValue;
-#undef CRN_GO
+// A unit's kernels are the rows of its table (crn_forms.h) and nothing else: U names the table (U::row(i), U::n).  This is the one
+// place Cfg's positional parameter list is written out.
+template <class U, size_t I>
+using FormAt = Cfg<U::row(I).r3, U::row(I).nbuf, true, U::row(I).nt, U::row(I).mag, U::row(I).win, U::row(I).tw2lds, U::row(I).occ, U::row(I).full, true, U::row(I).opt>;
+
+template <class U, size_t I>
+static hipError_t launch_row(const SenseParams &p, hipStream_t stream) {
+  using C = FormAt<U, I>;
+  constexpr FormKey k = U::row(I);
+  static_assert(C::R3 == k.r3 && C::NBUF == k.nbuf && C::PREFETCH && C::NT == k.nt && C::MAG == k.mag && C::WIN == k.win && C::TW2LDS == k.tw2lds &&
+                C::OCC == k.occ && C::FULL == k.full && C::PK && C::OPT == k.opt, "FormAt<U, I> is row I of the table, field for field");
+  if constexpr (k.dealt) return launch_dealt_cfg<C>(p, stream);
+  else return launch_cfg<C>(p, stream);
+}
+template <class U, size_t... I>
+static hipError_t launch_form(const FormKey &k, const SenseParams &p, hipStream_t stream, std::index_sequence<I...>) {
+  hipError_t e = hipErrorInvalidValue;   // (not a row of this unit)
+  (void)((U::row(I) == k && ((e = launch_row<U, I>(p, stream)), true)) || ...);
+  return e;
 }
 
-// The plain 4096-point kernel's forms (energy mode, no window, L = N): the default and its unpruned form.
-template <int R3, int NBUF, bool PREFETCH, bool NT, bool TW2LDS, int OCC, bool PK, int OPT = 0>
-static hipError_t launch_rn(const SenseParams &p, bool, bool, hipStream_t stream) {
-  return launch_cfg<Cfg<R3, NBUF, PREFETCH, NT, false, false, TW2LDS, OCC, true, PK, OPT>>(p, stream);
+// A launch: the rule names the form (crn_forms.cpp: select_form), the unit launches that row.
+template <class U>
+static hipError_t launch_selected(const SenseParams &p, FormQuery q, hipStream_t stream, int *deal_rounds_run) {
+  constexpr auto rows = std::make_index_sequence<U::n>{};
+  std::optional<FormKey> k = select_form(q);
+  if (!k) return hipErrorInvalidValue;
+  const hipError_t e = launch_form<U>(*k, p, stream, rows);
+  if (!k->dealt) return e;
+  if (e != hipErrorLaunchOutOfResources) {
+    if (e == hipSuccess && deal_rounds_run) *deal_rounds_run = p.deal_rounds;
+    return e;
+  }
+  SenseParams s = p;   // the device refused the LDS the frame slots need (launch_dealt_cfg): the streaming form takes it
+  s.deal_rounds = 0;
+  q.dealt = false;
+  k = select_form(q);
+  return k ? launch_form<U>(*k, s, stream, rows) : hipErrorInvalidValue;
 }
-
 
 }  // namespace crn
 #endif

@@ -18,7 +18,7 @@ LDS_BUDGET = 160 * 1024                                    # per workgroup on gf
 
 
 def has_dealt_form(cfg, L=None, lds_budget=LDS_BUDGET):
-    """The rule of crn::sense_deal_rounds (csrc/crn_kernels.hip) restated: 512 / 1024 points, at least two frames to deal, no window
+    """The rule of crn::sense_deal_rounds (csrc/crn_forms.cpp) restated: 512 / 1024 points, at least two frames to deal, no window
     (any packet length, both modes) or the periodic Hann in energy mode on whole frames, and the frame slots fit the workgroup's LDS.
     (A handle with CFAR on has no dealt form either; a cfg does not say.)"""
     n, K = cfg.fft_len, cfg.frames_per_epoch
@@ -32,7 +32,7 @@ def has_dealt_form(cfg, L=None, lds_budget=LDS_BUDGET):
     t = 16 * r3
     groups = 256 // t
     rounds = (K + groups - 1) // groups
-    # exchange buffers + pass-2 twiddles, kCloseLdsBytes (crn_epoch_close.h: kBandTabWords = 656 words of crn_kernels.h + 8 x 16 floats), frame slots
+    # exchange buffers + pass-2 twiddles, kCloseLdsBytes (crn_forms.h: kBandTabWords = 656 words of crn_kernels.h + 8 x 16 floats), frame slots
     lds = (groups * 16 * (t + r3) + 16 * r3) * 8 + (656 * 4 + 8 * 16 * 4) + rounds * groups * n * (4 if mag else 8)
     return lds <= lds_budget
 

@@ -18,7 +18,7 @@
 
 #include "../../include/crn_sense.h"
 #include "../../include/crn_sense_sc16.h"
-#include "../../cognitive-radio-network_amd/csrc/crn_kernels.h"
+#include "../../cognitive-radio-network_amd/csrc/crn_forms.h"
 
 std::atomic<long long> g_fake_gpu_latency_ns{0};
 
@@ -44,18 +44,11 @@ hipError_t launch_sense(const SenseParams &p, int fft_len, bool, bool, int, hipS
   g_launches++;
   return hipSuccess;
 }
-int sense_num_variants() { return 27; }
 std::atomic<long long> g_warm{0};
 }
 std::atomic<long> g_pauses{0};
 namespace crn {
 hipError_t launch_nop(hipStream_t) { g_warm++; return hipSuccess; }   // crn_sense_warm_stream: the launcher thread's empty launch at a pre-wake
-int sense_deal_rounds(int, bool, bool, bool, int, size_t) { return 0; }
-unsigned sense_ref_acc_mask(int) { return 0xFFFFu; }
-bool sense_variant_available(int v) { return v == 0; }
-bool sense_variant_traces(int) { return false; }
-void sense_variant(int, int, int *a, int *b, int *c, int *d, int *e) { *a = *b = *c = *e = 1; *d = 0; }
-void sense_geometry(int fft_len, int, int *t, int *l, int *e) { *t = 256; *l = 0; *e = 256 / (fft_len / 16); }
 hipError_t launch_fft(const FftParams &, int, hipStream_t) { return hipSuccess; }
 hipError_t launch_monitor(const MonitorParams &, hipStream_t) { return hipSuccess; }
 hipError_t launch_noise_floor(const float *feat, int n, int nb, float *scratch, hipStream_t) {

@@ -2,7 +2,7 @@
 // (kTw1C: rows 9..15 of pass 1 are the negative frequencies a - 16, so register row d of a thread covers bins [256 d - 7, 256 d + 249),
 // csrc/crn_kernels.h: lane_coord / bin_of), checked the way api_unit.cpp checks the unshifted ones — and that the unshifted entries and
 // mask are still what they were.  Host sources compiled as they are against tests/harness/fake_hip; the launch functions are stand-ins
-// that record the parameter block.  Built and run by tests/test_negative_frequency_rows_host.py; nothing of this is linked into the product.
+// that record the parameter block; csrc/crn_forms.cpp (the forms and the rule crn_sense_kernel_info prints from) is linked as it is.  Built and run by tests/test_negative_frequency_rows_host.py; nothing of this is linked into the product.
 #include <hip/hip_runtime.h>
 
 #include <cstdio>
@@ -13,7 +13,7 @@
 
 #include "../../include/crn_sense.h"
 #include "../../include/crn_sense_sc16.h"
-#include "../../cognitive-radio-network_amd/csrc/crn_kernels.h"
+#include "../../cognitive-radio-network_amd/csrc/crn_forms.h"
 
 std::atomic<long long> g_fake_gpu_latency_ns{0};
 
@@ -29,14 +29,7 @@ hipError_t launch_sense(const SenseParams &p, int, bool, bool, int, hipStream_t,
   g_launches++;
   return hipSuccess;
 }
-int sense_num_variants() { return 27; }
 hipError_t launch_nop(hipStream_t) { return hipSuccess; }
-int sense_deal_rounds(int, bool, bool, bool, int, size_t) { return 0; }
-unsigned sense_ref_acc_mask(int fft_len) { return fft_len == 512 ? 0x85e1u : fft_len == 1024 ? 0xbf73u : fft_len == 2048 ? 0x9f9bu : 0x8267u; }
-bool sense_variant_available(int v) { return v == 0 || v == 13 || v == 2; }
-bool sense_variant_traces(int) { return false; }
-void sense_variant(int fft_len, int, int *nbuf, int *prefetch, int *nt, int *tw2lds, int *pk) { *nbuf = 1; *prefetch = 1; *nt = 1; *tw2lds = fft_len == 4096; *pk = 1; }
-void sense_geometry(int fft_len, int, int *threads, int *lds_bytes, int *epochs_per_block) { *threads = 256; *lds_bytes = 0; *epochs_per_block = 256 / (fft_len / 16); }
 hipError_t launch_fft(const FftParams &, int, hipStream_t) { return hipSuccess; }
 hipError_t launch_monitor(const MonitorParams &, hipStream_t) { return hipSuccess; }
 hipError_t launch_noise_floor(const float *, int, int, float *, hipStream_t) { return hipSuccess; }

@@ -395,7 +395,7 @@ def test_plan_pruned_kernels_equal_the_full_ones(built, n, mode):
     only the registers that plan reaches (7 / 12 / 11 / 7 of 16 at N = 512 / 1024 / 2048 / 4096); variant 2 runs the full kernels.
     Same operations on the kept bins: features, network outputs, decisions and occupancy are bit-identical — whole frames and, in |X|
     mode, the radio's 364-sample packets.  (Energy mode on short packets: the reference-plan form closes from registers, what any
-    other plan runs closes through the LDS walk — csrc/crn_sense_kernel.h, register_close — so the band sums come in another order
+    other plan runs closes through the LDS walk — csrc/crn_forms.cpp, register_close — so the band sums come in another order
     and agree to rounding, 2e-6.)  A band table that reaches other registers silently gets the full kernel (checked against the
     oracle)."""
     cfg = cs.cfg_energy_scaled(n, 4.0) if mode == "energy" else cs.cfg_reference_scaled(n)

@@ -10,7 +10,7 @@ import subprocess
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HARNESS = os.path.join(ROOT, "tests", "harness")
 CSRC = os.path.join(ROOT, "cognitive-radio-network_amd", "csrc")
-API_SRCS = ["crn_api.cpp", "crn_tables.cpp", "crn_updates.cpp", "crn_cfar.cpp", "crn_api_sc16.cpp", "crn_cfg.cpp"]   # as tests/harness/Makefile: api_unit
+API_SRCS = ["crn_api.cpp", "crn_tables.cpp", "crn_updates.cpp", "crn_cfar.cpp", "crn_api_sc16.cpp", "crn_cfg.cpp", "crn_forms.cpp"]   # as tests/harness/Makefile: api_unit
 
 
 def test_shifted_row_entries_rebuild_every_plan(tmp_path):

@@ -5,8 +5,8 @@ other small 512 / 1024-point test in tests/ checks that kernel; what bench.py ti
 every large batch runs — is the streaming kernel, where one wave holds two (512) or one (1024) lane groups and no barrier separates
 the exchanges.  Here every case selects the streaming form through tests/forms.py and asserts that no launch was dealt.
 
-FORMS lists what is pinned, each by the Cfg<R3, NBUF, PREFETCH, NT, MAG, WIN, TW2LDS, OCC, FULL, PK, OPT> it instantiates
-(launch_r in csrc/crn_kernels.hip, launch_default in csrc/crn_sense_kernel.h; kBase = kSpread | kLdsBlk | kPrioValu | kMulti).
+FORMS lists what is pinned, each by the row of the table of compiled forms it runs, written as csrc/crn_forms.h writes it
+(add_forms_of_size; select_form in csrc/crn_forms.cpp picks it; r3 = N / 256).
 
 Shapes: K in {1, 2, 3, 10} (no averaging; the ping-pong frame loop's even and odd ends); L in {N, 364, 363, 1} where the form takes short
 packets; 100 epochs at N = 512 and 50 at N = 1024 = 13 epoch groups, the last one with 4 / 2 live epochs (and 97 / 49 epochs: a last
@@ -123,25 +123,25 @@ def _welch(n):
     return cs.cfg_welch(n, 8, 64)
 
 
-# name -> (cfg maker, packet lengths, spectrum request, layout).  The comment names the kernel: Cfg<R3, 1, true, true, MAG, WIN, TW2LDS, 3, FULL, true, OPT>
+# name -> (cfg maker, packet lengths, spectrum request, layout).  The comment names the kernel: its row of csrc/crn_forms.h
 FORMS = {
     # the reference plan: pass 3 and the accumulate pruned to its rows, band sums from registers
-    "ref_mag_whole": (_ref_mag, _whole, False, "dense"),            # Cfg<.., true,  false, false, 3, true,  .., kBase | kRegBands | kRows>
-    "ref_mag_short": (_ref_mag, lambda n: _short(n)[1:], False, "dense"),        # Cfg<.., true,  false, false, 3, false, .., kBase | kRegBands | kRows>
-    "ref_energy_whole": (_ref_energy, _whole, False, "dense"),      # Cfg<.., false, false, false, 3, true,  .., kBase | kRegBands | kRows>
-    "ref_energy_short": (_ref_energy, lambda n: _short(n)[1:], False, "dense"),  # Cfg<.., false, false, false, 3, false, .., kBase | kRegBands | kRows>
+    "ref_mag_whole": (_ref_mag, _whole, False, "dense"),            # streaming(r3, kRegBands | kRows).magnitude().whole()
+    "ref_mag_short": (_ref_mag, lambda n: _short(n)[1:], False, "dense"),        # streaming(r3, kRegBands | kRows).magnitude()
+    "ref_energy_whole": (_ref_energy, _whole, False, "dense"),      # streaming(r3, kRegBands | kRows).whole()
+    "ref_energy_short": (_ref_energy, lambda n: _short(n)[1:], False, "dense"),  # streaming(r3, kRegBands | kRows)
     # a small plan with a bin outside the reference rows (test_dealt_frames._plans "other plan"): all rows, register close on whole
     # frames, the LDS walk on short packets
-    "other_plan_whole": (_plan_of("other plan"), _whole, False, "dense"),                     # Cfg<.., false, false, false, 3, true,  .., kBase | kRegBands>
-    "other_plan_short": (_plan_of("other plan"), lambda n: _short(n)[1:], False, "dense"),    # Cfg<.., false, false, false, 3, false, .., kBase>
+    "other_plan_whole": (_plan_of("other plan"), _whole, False, "dense"),                     # streaming(r3, kRegBands).whole()
+    "other_plan_short": (_plan_of("other plan"), lambda n: _short(n)[1:], False, "dense"),    # streaming(r3)
     # 16 bands (no row entries) and spectrum requests: the LDS walk
-    "sixteen_bands": (_plan_of("16 bands"), _short, False, "dense"),            # Cfg<.., false, false, false, 3, true / false, .., kBase>
-    "spectrum_energy": (_ref_energy, _short, True, "dense"),        # Cfg<.., false, false, false, 3, true / false, .., kBase>
-    "spectrum_mag": (_ref_mag, _short, True, "dense"),              # Cfg<.., true,  false, false, 3, false, .., kBase>
+    "sixteen_bands": (_plan_of("16 bands"), _short, False, "dense"),            # streaming(r3).whole() / streaming(r3)
+    "spectrum_energy": (_ref_energy, _short, True, "dense"),        # streaming(r3).whole() / streaming(r3)
+    "spectrum_mag": (_ref_mag, _short, True, "dense"),              # streaming(r3).magnitude()
     # the table window (Blackman-Harris), pass-2 twiddles in LDS
-    "bh_energy": (_windowed(_ref_energy, cs.WINDOW_BLACKMAN_HARRIS), _whole, True, "dense"),  # Cfg<.., false, true, true, 3, false, .., kBase>
-    "bh_mag": (_windowed(_ref_mag, cs.WINDOW_BLACKMAN_HARRIS), _whole, True, "dense"),        # Cfg<.., true,  true, true, 3, false, .., kBase>
-    # periodic Hann, whole frames, energy mode: Cfg<.., false, true, true, 3, true, .., kBase | kHannSym | kTw2Early>
+    "bh_energy": (_windowed(_ref_energy, cs.WINDOW_BLACKMAN_HARRIS), _whole, True, "dense"),  # streaming(r3).window().tw2_from_lds()
+    "bh_mag": (_windowed(_ref_mag, cs.WINDOW_BLACKMAN_HARRIS), _whole, True, "dense"),        # streaming(r3).window().tw2_from_lds().magnitude()
+    # periodic Hann, whole frames, energy mode: streaming(r3, kHannSym | kTw2Early).window().tw2_from_lds().whole()
     "hann_disjoint": (_windowed(_ref_energy, cs.WINDOW_HANN), _whole, True, "dense"),   # disjoint frames: the plain stream
     "hann_welch": (_welch, _whole, True, "dense"),                                      # hop N/2, dense epochs: launch_cfg's welch_stream
     "hann_welch_gaps": (_welch, _whole, True, "gaps"),                                  # hop N/2, epoch_stride > an epoch: the non-multi path

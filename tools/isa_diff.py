@@ -3,7 +3,7 @@
 
 For refactors of the kernel headers that must not change what the shipped kernels execute: every kernel function of `old` is
 looked up in `new` by its demangled name and the two instruction streams are compared line by line, comments and metadata
-stripped, local labels (.LBBn_m) renamed by order of first appearance so that a different function order does not matter.
+stripped, local labels (.LBBn_m, .Lpost_getpcN) renamed by order of first appearance so that a different function order does not matter.
 
   --drop-cfg-arg N   remove the N-th (0-based) argument of every `crn::Cfg<...>` in OLD names before matching (a template
                      parameter the refactor deleted)
@@ -18,7 +18,7 @@ import subprocess
 import sys
 
 CXXFILT = "c++filt"   # binutils (llvm-cxxfilt is not in the ROCm image)
-LABEL = re.compile(r"\.L(BB|func_end|func_begin|tmp)?[0-9_]+")
+LABEL = re.compile(r"\.L(BB|func_end|func_begin|tmp|post_getpc)?[0-9_]+")   # (post_getpc: long-branch labels, numbered across the whole unit)
 
 
 def functions(path):
