@@ -27,7 +27,18 @@ namespace crn {
 // Epoch close (reference .cpp:157-261 + the reset at :287-288): K-frame averages -> LDS in natural
 // bin order -> band sums -> features -> decision.  Resets the accumulators for the next epoch.
 // ---------------------------------------------------------------------------------------------
-// (LDS behind the exchange buffers and the tw2 table, used by the epoch close: kCloseLdsBytes, crn_forms.h)
+// (where the close's LDS lies — a lane group's exchange buffers, the band-table copy, the team partials: lds_layout, crn_forms.h)
+
+// What the LDS form of the close keeps behind a lane group's image of the spectrum (N + N / 16 floats over the group's exchange
+// buffers), in floats from the image's start
+template <int R3>
+struct CloseImage {
+  static constexpr int kFeat = spec_phys(Geo<R3>::N);     // [CRN_MAX_BANDS = 80] features
+  static constexpr int kBlk = kFeat + 80;                 // [T] totals of the 16-bin blocks
+  static constexpr int kRows = kBlk + Geo<R3>::T;         // [R3] totals of the 256-bin rows
+  static constexpr int kMask = kRows + R3;                // CFAR: [N / 16] half-words = [N / 32] words of detected bins
+  static constexpr int kCnt = kMask + Geo<R3>::N / 32;    // CFAR: [n_bands] detected bins per band
+};
 
 // LDS address-space views for the epoch close (see epoch_close): ds_* instructions, lgkmcnt only.
 typedef __attribute__((address_space(3))) float lds_f32;
@@ -142,6 +153,7 @@ CRN_DEV void epoch_close(FrameCtx<C> &c, const SenseParams &p, long long epoch_b
   constexpr bool MAG = C::MAG;
   using G = Geo<R3>;
   constexpr int T = G::T, N = G::N, J = G::J;
+  constexpr LdsLayout kLds = lds_layout(R3, C::NBUF, (C::OPT & kDeal) != 0);
   float (&acc)[16] = c.acc;
   const float Kf = c.Kf;
   // Everything this block needs is re-derived here from uniform values (SGPRs) and the hardware
@@ -166,18 +178,19 @@ CRN_DEV void epoch_close(FrameCtx<C> &c, const SenseParams &p, long long epoch_b
   // The opaque values are 32-bit LDS offsets, not generic pointers: through a generic pointer every
   // access below became a FLAT instruction followed by s_waitcnt vmcnt(0), which also drained the
   // next frame's prefetch at every epoch close.
-  const unsigned tab_off = c.lds_base + (unsigned)((G::GROUPS * C::NBUF * G::GROUP_CPLX + 16 * R3) * sizeof(cx));
-  const unsigned gb_off = c.lds_base + (unsigned)grp * (unsigned)(C::NBUF * G::GROUP_CPLX * sizeof(cx));
+  const unsigned tab_off = c.lds_base + (unsigned)kLds.tab;
+  const unsigned gb_off = c.lds_base + (unsigned)grp * (unsigned)kLds.group_bytes;
   const lds_i32 *tab = reinterpret_cast<const lds_i32 *>(tab_off);
   const lds_f32 *thr = reinterpret_cast<const lds_f32 *>(tab_off + kTabThresh * 4);
   const lds_f64 *w_ih = reinterpret_cast<const lds_f64 *>(tab_off + kTabWih * 4);  // [5][6]
   const lds_f64 *w_ho = reinterpret_cast<const lds_f64 *>(tab_off + kTabWho * 4);  // [6][4]
   lds_f32 *spec = reinterpret_cast<lds_f32 *>(gb_off);    // N + N/16 floats
-  lds_f32 *featl = spec + spec_phys(N);                   // CRN_MAX_BANDS floats (LDS path)
+  using Img = CloseImage<R3>;
+  lds_f32 *featl = spec + Img::kFeat;
   constexpr int TEAM = G::TEAM;
   constexpr int TPG = T / TEAM;  // teams (waves) per group
   const int lane = t % TEAM;
-  lds_f32 *part = reinterpret_cast<lds_f32 *>(tab_off + kBandTabWords * 4);  // [256 / TEAM][16]
+  lds_f32 *part = reinterpret_cast<lds_f32 *>(tab_off + (unsigned)(kLds.part - kLds.tab));  // [256 / TEAM][16]
   [[maybe_unused]] const lds_f32 *feat = nullptr;
   // Three forms of the close, chosen per launch (one kernel holding several spilled in the frame loop):
   static_assert((C::OPT & kCfar) == 0 || (C::OPT & (kAlignedBands | kRegBands | kRows | kDeal)) == 0, "CFAR runs in the LDS form of the close");
@@ -389,8 +402,7 @@ CRN_DEV void epoch_close(FrameCtx<C> &c, const SenseParams &p, long long epoch_b
     //   ascending like the reference) -> blk[t]; the 16 lanes of a DPP row add their block totals
     //   -> rows[t / 16] (256 bins);  then ONE LANE PER BAND walks its segments in steps of 256, 16
     //   and 1 bins (at most 15 + 15 + 16 + 15 + 15 reads), all bands at once.
-    lds_f32 *blk = featl + 80;  // [T] block totals (behind the CRN_MAX_BANDS features)
-    lds_f32 *rows = blk + T;                 // [R3] row totals
+    lds_f32 *blk = spec + Img::kBlk, *rows = spec + Img::kRows;
     {
       float bs = 0.f;
 #pragma unroll
@@ -475,9 +487,9 @@ CRN_DEV void epoch_close(FrameCtx<C> &c, const SenseParams &p, long long epoch_b
     [[maybe_unused]] const lds_i32 *cfar_cnt = nullptr;
     if constexpr ((C::OPT & kCfar) != 0) {
       static_assert(!MAG && !C::SC16, "CFAR: energy mode, float samples");
-      lds_u16 *mk16 = reinterpret_cast<lds_u16 *>(rows + R3);        // [N / 16] half-words = [N / 32] words, behind the row totals
-      const lds_u32 *mk32 = reinterpret_cast<const lds_u32 *>(rows + R3);
-      lds_i32 *cnt = reinterpret_cast<lds_i32 *>(rows + R3 + N / 32);  // [n_bands]
+      lds_u16 *mk16 = reinterpret_cast<lds_u16 *>(spec + Img::kMask);
+      const lds_u32 *mk32 = reinterpret_cast<const lds_u32 *>(spec + Img::kMask);
+      lds_i32 *cnt = reinterpret_cast<lds_i32 *>(spec + Img::kCnt);
       const int g = p.cfar_guard, W = p.cfar_train;
       const int k0 = 16 * t;
       const int yl = k0 - g - W, zl = k0 + g + 1;   // first cell of the left / right run

@@ -29,14 +29,12 @@ int sense_deal_rounds(int fft_len, bool mag, bool win, bool hann_whole_frames, i
   if (K < 2) return 0;   // one frame: nothing to deal
   const int r3 = fft_len / 256, groups = 256 / (16 * r3);
   const int rounds = (K + groups - 1) / groups;
-  const size_t lds = (size_t)form_geometry(dealt_frames(r3)).lds_bytes + (size_t)rounds * groups * fft_len * (mag ? 4 : 8);   // + the frame slots
+  const size_t lds = lds_layout(r3, 1, true).bytes_with_slots(rounds, mag);
   return lds <= lds_budget ? rounds : 0;
 }
 
 FormGeometry form_geometry(const FormKey &k) {
-  const int t = 16 * k.r3, groups = 256 / t;
-  // exchange buffers ([16][T + R3] complex per lane group and buffer), the pass-2 twiddle table, the close's share
-  return FormGeometry{256, (groups * k.nbuf * 16 * (t + k.r3) + 16 * k.r3) * 8 + kCloseLdsBytes, k.dealt ? 1 : groups};
+  return FormGeometry{256, lds_layout(k.r3, k.nbuf, k.dealt).bytes, k.dealt ? 1 : 256 / (16 * k.r3)};
 }
 
 void form_name(const FormKey &k, char *name, size_t name_len) {

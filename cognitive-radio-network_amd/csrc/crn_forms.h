@@ -66,6 +66,32 @@ static_assert(ref_acc_mask_shifted(16, kTw1cRowShift) == kRefPlanRows, "N = 4096
 // then [8 teams][16] per-team band partials of the register path.
 constexpr int kCloseLdsBytes = kBandTabWords * 4 + 8 * 16 * 4;
 
+// The sensing kernel's dynamic LDS, stated once for the kernels, their launches and crn_sense_kernel_info: byte offsets from the start
+// of the segment for a form of size r3 with nbuf exchange buffers, streaming or dealt.
+struct LdsLayout {
+  int group_bytes;   // a lane group's exchange buffers, nbuf x [16][T + R3] complex: group g's at g * group_bytes (the LDS close lays its
+                     // image of the spectrum over them)
+  int tw2;           // [16][R3] complex: the pass-2 twiddle table (read by the TW2LDS forms; every form leaves the room)
+  int tab;           // the band-table copy, kBandTabWords words
+  int part;          // [8 teams][16] floats: per-team band partials of the register close
+  int bytes;         // all of the above: what a streaming launch asks for
+  int slots;         // dealt forms: the frame slots, [rounds x lane groups] of N per-bin values each (0: a streaming form has none)
+  int round_values;  // values one round of slots holds: lane groups x N
+  constexpr size_t bytes_with_slots(int rounds, bool mag) const { return (size_t)bytes + (slots != 0 ? (size_t)rounds * round_values * (mag ? 4 : 8) : 0); }
+};
+constexpr LdsLayout lds_layout(int r3, int nbuf, bool dealt) {
+  const int t = 16 * r3, groups = 256 / t, cplx = 8;
+  LdsLayout l{};
+  l.group_bytes = nbuf * 16 * (t + r3) * cplx;
+  l.tw2 = groups * l.group_bytes;
+  l.tab = l.tw2 + 16 * r3 * cplx;
+  l.part = l.tab + kBandTabWords * 4;
+  l.bytes = l.tab + kCloseLdsBytes;
+  l.slots = dealt ? l.bytes : 0;
+  l.round_values = groups * 256 * r3;
+  return l;
+}
+
 // A compiled form: one row of a unit's table
 // (Cfg's PREFETCH and PK are true in every form.)  The with-functions let a table row and the rule below name what a form has
 // instead of listing ten positional values.

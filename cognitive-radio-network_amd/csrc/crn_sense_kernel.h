@@ -40,6 +40,12 @@ CRN_DEV StreamSpan stream_span(const SenseParams &p) {
   return s;
 }
 
+// a place in the dynamic LDS segment
+template <class T>
+CRN_DEV T *lds_at(cx *lds, int byte_off) {   // (the offsets: lds_layout, crn_forms.h; every one a whole number of complex values)
+  return reinterpret_cast<T *>(lds + byte_off / (int)sizeof(cx));
+}
+
 // ---------------------------------------------------------------------------------------------
 // the sensing kernel
 // ---------------------------------------------------------------------------------------------
@@ -50,6 +56,7 @@ __global__ __launch_bounds__(256, C::OCC) void sense_kernel(const SenseParams p)
   constexpr unsigned SB = C::SB;
   using G = Geo<R3>;
   constexpr int T = G::T;
+  constexpr LdsLayout kLds = lds_layout(R3, NBUF, false);
   extern __shared__ __attribute__((aligned(16))) cx lds[];
 
   const int tid = threadIdx.x;
@@ -63,11 +70,11 @@ __global__ __launch_bounds__(256, C::OCC) void sense_kernel(const SenseParams p)
   c.a = a;
   c.m_lo = m_lo;
   c.L = p.L;
-  c.gbuf = lds + grp * (NBUF * G::GROUP_CPLX);
+  c.gbuf = lds + grp * (kLds.group_bytes / (int)sizeof(cx));
   c.wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   c.grp_epoch_stride = 1;
   c.lds_base = (unsigned)__builtin_amdgcn_readfirstlane((int)lds_offset(lds));
-  c.tw2_lds = lds + G::GROUPS * NBUF * G::GROUP_CPLX;  // [16][R3], TW2LDS only
+  c.tw2_lds = lds_at<cx>(lds, kLds.tw2);  // [16][R3], TW2LDS only
   CloseTrace<C>::workgroup_start(p, tid);   // (measurement build only: crn_frame_ab.h)
   const int K = p.K;
   c.Kf = (float)K;
@@ -91,6 +98,8 @@ __global__ __launch_bounds__(256, C::OCC) void sense_kernel(const SenseParams p)
 #pragma unroll
   for (int i = 1; i < ((C::OPT & kTw1C) != 0 ? 9 : 16); i++) c.tw1[i] = reinterpret_cast<const cx *>(p.tw1)[i * T + t];
   // (register-resident tables are requested ahead of the barrier too: nothing after it starts another round trip)
+  // (the window registers and the band-table staging stay written out in both kernels: as shared helpers they changed VGPR counts and
+  // scratch sizes of windowed kernels, and the staging's clamped index compiled to other instructions in every kernel — tools/isa_diff.py)
   if constexpr (!C::TW2LDS) {
 #pragma unroll
     for (int i = 1; i < 16; i++) c.tw2[i] = reinterpret_cast<const cx *>(p.tw2)[i * R3 + m_lo];
@@ -106,7 +115,7 @@ __global__ __launch_bounds__(256, C::OCC) void sense_kernel(const SenseParams p)
     // band table -> LDS (2 KiB behind the exchange buffers and the tw2 table): the epoch close walks
     // it, and from global memory every walk step was a dependent ~1 us vector load.  Every load of the prologue is issued before the
     // first LDS write (unconditional loads, clamped indices): one wait for all of them instead of three round trips in a row.
-    int *tab = reinterpret_cast<int *>(lds + G::GROUPS * NBUF * G::GROUP_CPLX + 16 * R3);
+    int *tab = lds_at<int>(lds, kLds.tab);
     const int w0 = p.band_tab[tid], w1 = p.band_tab[tid + 256];
     const int w2 = p.band_tab[tid < kBandTabWords - 512 ? tid + 512 : kBandTabWords - 1];  // row entries
     [[maybe_unused]] cx tw2v = cx{0.f, 0.f};
@@ -115,7 +124,7 @@ __global__ __launch_bounds__(256, C::OCC) void sense_kernel(const SenseParams p)
     tab[tid + 256] = w1;
     if (tid < kBandTabWords - 512) tab[tid + 512] = w2;
     if constexpr (C::TW2LDS) {
-      if (tid < 16 * R3) lds[G::GROUPS * NBUF * G::GROUP_CPLX + tid] = tw2v;
+      if (tid < 16 * R3) (lds_at<cx>(lds, kLds.tw2))[tid] = tw2v;
     }
   }
   __syncthreads();
@@ -265,6 +274,7 @@ __global__ __launch_bounds__(256, 1) void sense_kernel_dealt(const SenseParams p
   constexpr unsigned SB = C::SB;
   using G = Geo<R3>;
   constexpr int T = G::T;
+  constexpr LdsLayout kLds = lds_layout(R3, 1, true);
   static_assert(!G::XWAVE && C::NBUF == 1 && !C::TW2LDS && (C::OPT & kDeal) != 0,
                 "dealt frames: N <= 1024, twiddles in registers");
   extern __shared__ __attribute__((aligned(16))) cx lds[];
@@ -278,10 +288,10 @@ __global__ __launch_bounds__(256, 1) void sense_kernel_dealt(const SenseParams p
   c.a = t / R3;
   c.m_lo = t % R3;
   c.L = p.L;
-  c.gbuf = lds + grp * G::GROUP_CPLX;
+  c.gbuf = lds + grp * (kLds.group_bytes / (int)sizeof(cx));
   c.wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   c.lds_base = (unsigned)__builtin_amdgcn_readfirstlane((int)lds_offset(lds));
-  c.tw2_lds = lds + G::GROUPS * G::GROUP_CPLX;
+  c.tw2_lds = lds_at<cx>(lds, kLds.tw2);
   // only lane group 0 holds an epoch when the close runs: the others' epoch index lands past the batch (inactive)
   c.grp_epoch_stride = (int)p.n_epochs;
   const int K = p.K;
@@ -316,7 +326,7 @@ __global__ __launch_bounds__(256, 1) void sense_kernel_dealt(const SenseParams p
     for (int r = 0; r < 16; r++) c.win[r] = p.window[t + T * r];
   }
   {
-    int *tab = reinterpret_cast<int *>(lds + G::GROUPS * G::GROUP_CPLX + 16 * R3);
+    int *tab = lds_at<int>(lds, kLds.tab);
     const int w0 = p.band_tab[tid], w1 = p.band_tab[tid + 256];
     const int w2 = p.band_tab[tid < kBandTabWords - 512 ? tid + 512 : kBandTabWords - 1];
     tab[tid] = w0;
@@ -328,8 +338,7 @@ __global__ __launch_bounds__(256, 1) void sense_kernel_dealt(const SenseParams p
 
   // frame slots behind everything the streaming kernel keeps in LDS: [rounds x GROUPS][16][T] values
   constexpr unsigned kSlotBytes = (unsigned)G::N * (C::MAG ? 4u : 8u);
-  const unsigned park_base =
-      c.lds_base + (unsigned)((G::GROUPS * G::GROUP_CPLX + 16 * R3) * sizeof(cx)) + (unsigned)kCloseLdsBytes;
+  const unsigned park_base = c.lds_base + (unsigned)kLds.slots;
   int r = 0;
 #define CRN_DEAL_STEP(CUR, NXT)                                                                       \
   {                                                                                                   \
@@ -352,10 +361,7 @@ __global__ __launch_bounds__(256, 1) void sense_kernel_dealt(const SenseParams p
 
 template <class C>
 static hipError_t launch_dealt_cfg(const SenseParams &p, hipStream_t stream) {
-  using G = Geo<C::R3>;
-  const size_t slot_bytes = (size_t)G::N * (C::MAG ? 4 : 8);
-  const size_t lds = ((size_t)G::GROUPS * G::GROUP_CPLX + 16 * C::R3) * sizeof(cx) + kCloseLdsBytes +
-                     (size_t)p.deal_rounds * G::GROUPS * slot_bytes;
+  const size_t lds = lds_layout(C::R3, 1, true).bytes_with_slots(p.deal_rounds, C::MAG);
   if (p.n_epochs <= 0) return hipSuccess;
   auto kfn = sense_kernel_dealt<C>;
   if (lds > 48 * 1024) {
@@ -401,7 +407,7 @@ static hipError_t launch_cfg(const SenseParams &p, hipStream_t stream) {
     q.tail_groups_per_wg = 1;
     grid = (unsigned)n_groups;
   }
-  const size_t lds = ((size_t)G::GROUPS * C::NBUF * G::GROUP_CPLX + 16 * C::R3) * sizeof(cx) + kCloseLdsBytes;
+  const size_t lds = (size_t)lds_layout(C::R3, C::NBUF, false).bytes;
   if (grid == 0) return hipSuccess;
   auto kfn = sense_kernel<C>;
   if (lds > 48 * 1024) {

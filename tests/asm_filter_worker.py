@@ -1,6 +1,7 @@
 """Child process of tests/test_asm_filter.py: run every kernel family of the library $CRN_SENSE_LIB names (libcrnsense.so /
 libcrnsense_sc16.so: built through csrc/strip_asm_nops.py; libcrnsense_plain.so: plain hipcc) on generated batches and print one JSON
-object {case: {output: sha256}} — the parent asserts that the filtered and the plain build give the same BYTES.
+object {case: {output: sha256}} — the parent asserts that the filtered and the plain build give the same BYTES.  The CFAR kernels'
+cases hash the bin mask and the per-band bin counts as well.
 
     python tests/asm_filter_worker.py [--big-gib 2.0]
 
@@ -66,6 +67,39 @@ def run_case(name, cfg, dev, n_epochs, L=None, variant=0, deal=400, want_spectru
     del iq, src, out
     torch.cuda.empty_cache()
     return res
+
+
+def run_cfar_case(name, cfg, dev, n_epochs, method, train, guard=2, seed=1):
+    """One launch of a CFAR handle (the LDS close with the CFAR pass): the outputs of run_case that exist with CFAR on, plus the bin mask
+    and the per-band bin counts."""
+    n, nb = cfg.fft_len, cfg.n_bands
+    iq = make_iq(cs.samples_needed(cfg, n_epochs, n), seed, dev)
+    s = cs.Sensor(cfg)
+    s.set_cfar(guard, train, cs.cfar_alpha(1e-3, cfg.frames_per_epoch, train, method), 1, method=method)
+    out = {"features": torch.full((n_epochs, nb), -1.0, device=dev),
+           "decision": torch.full((n_epochs,), -7, dtype=torch.int32, device=dev),
+           "occupancy": torch.full((n_epochs, nb), 9, dtype=torch.uint8, device=dev),
+           "mask": torch.full((n_epochs, n // 32), -1, dtype=torch.int32, device=dev),
+           "band_bins": torch.full((n_epochs, nb), -1, dtype=torch.int32, device=dev)}
+    ptrs = {"features": out["features"].data_ptr(), "ann_out": 0, "decision": out["decision"].data_ptr(),
+            "occupancy": out["occupancy"].data_ptr(), "spectrum": 0}
+    s.run_device_cfar(iq.data_ptr(), n_epochs, n, ptrs, mask_ptr=out["mask"].data_ptr(), band_bins_ptr=out["band_bins"].data_ptr())
+    torch.cuda.synchronize()
+    info = {"kernel": s.kernel_info()["name"], "dealt_launches": s.dealt_launches(), "input_bytes": int(iq.numel() * iq.element_size())}
+    s.close()
+    res = {k: sha(v) for k, v in out.items()}
+    res["_info"] = info
+    return res
+
+
+def cfar_cases():
+    """The CFAR kernels: N = 512 (two lane groups share a wave, teams of 32 lanes) and 4096 (barriers across waves); 67 epochs (not a
+    multiple of the 8 lane groups of a 512-point workgroup); guard 2; 8 training cells per side (the fp64 sliding sums) and 24 (the
+    W >= 16 path); every method."""
+    for n in (512, 4096):
+        for train in (8, 24):
+            for method in ("ca", "go", "so", "os"):
+                yield f"cfar {method} {n}, train {train}", dict(cfg=cs.cfg_energy_scaled(n, 4.0), n_epochs=67, method=method, train=train)
 
 
 def cases(big_gib):
@@ -149,6 +183,8 @@ def main():
     res = {"_library": os.path.basename(cs.LIB_PATH)}
     for i, (name, kw) in enumerate(cases(a.big_gib)):
         res[name] = run_case(name, dev=dev, seed=100 + i, **kw)
+    for i, (name, kw) in enumerate(cfar_cases()):
+        res[name] = run_cfar_case(name, dev=dev, seed=300 + i, **kw)
     res["forward FFT"] = fft_case(dev)
     print(json.dumps(res))
 
