@@ -531,6 +531,70 @@ CRN_API int crn_channels_device(crn_handle *h, const uint32_t *d_bin_mask, const
  * negative or non-finite prior. */
 CRN_API int crn_channel_forecast(const crn_channel_stats *s, int32_t horizon, double prior, double *p01, double *p10, double *p_idle);
 
+/* -- cooperative sensing: the masks and spectra of a group of sensors fused into one ------------------------------------------
+ * Every stage above works on one stream, one node's receiver.  This one combines what a group of sensors on the same band, aligned in
+ * time, saw: M rows in, one row out.  A batch is laid out as for crn_tracks_device: n_epochs = S T, S streams of T = epochs_per_stream
+ * epochs in time order; M = group_size, S = G M, and group j is the streams j M .. j M + M - 1.  Fused row r = j T + t is formed from
+ * the member epochs (j M + m) T + t, m = 0 .. M - 1; N = fft_len.  The outputs have the layout of a batch of G streams, so they feed
+ * crn_segments_device, crn_tracks_device, crn_tracks_carry_device and crn_channels_device unchanged, with n_epochs = G T.
+ *   Active members   member m is active when weight[m] > 0; at least one must be.  An inactive member takes no part in anything: its
+ *                    rows and mask words are never read, so whatever they hold (a NaN, say) reaches no output.
+ *   Fused row        written whenever d_spectrum and d_fused_spectrum are given, under either rule:
+ *                      F[k] = fl32( sum (double)w_m (double)P_m[k] ), over the active m in ascending order, accumulated in fp64 and
+ *                    rounded to fp32 once.  (A product of two fp32 values is exact in fp64: a fused multiply-add and a separate
+ *                    multiply and add give the same bits.)  The weights are not normalised: equal-gain combining is w_m = 1 / M, and
+ *                    a caller who knows the members' noise floors passes their reciprocals.
+ *   CRN_FUSE_VOTE    hard decision: fused bit k is set when at least `votes` active members have bit k set.  OR is votes = 1, AND is
+ *                    votes = n_active, majority is votes = ceil(n_active / 2).  Needs d_bin_mask; the spectrum is optional.
+ *   CRN_FUSE_SOFT    CA-CFAR on the fused row, every sum direct and in a fixed order.  With g = guard, W = train:
+ *                      L = sum over i = g + 1 .. g + W, ascending, of (double)F[(k - i) mod N];  R the same with k + i;  T = L + R
+ *                      bin k detected  <=>  (double)F[k] 2W > (double)alpha T   (fp64)
+ *                    No sliding sum and no difference of prefix sums: a strong bin that enters and leaves such a sum leaves a residue
+ *                    behind.  Needs d_spectrum; d_fused_spectrum may be NULL (the fused row then never leaves the chip); d_bin_mask
+ *                    is optional.
+ *                    alpha = crn_cfar_alpha(pfa, n_active K, W) holds the false-alarm rate at `pfa` under that function's noise model
+ *                    with equal weights and equal noise power at every member: the mean of n_active independent K-frame means is
+ *                    Gamma(n_active K).  Sensors with unequal floors, or correlated sensors, move the real rate.
+ *   Row header       n_detected = set bits of the fused mask; n_any = bins set in at least one active member's mask, n_all = bins set
+ *                    in all of them (both 0 without d_bin_mask: together they show how much the sensors disagree); n_active.
+ *   Cut independence a batch gives the same bytes however it is cut along time or along groups. */
+#define CRN_MAX_FUSE_MEMBERS 32
+typedef enum crn_fuse_rule { CRN_FUSE_VOTE = 0, CRN_FUSE_SOFT = 1 } crn_fuse_rule;
+typedef struct crn_fuse_params {
+  int32_t rule, group_size, epochs_per_stream;
+  int32_t votes;                      /* VOTE: k in 1..n_active.  SOFT: 0 */
+  int32_t guard, train;               /* SOFT: crn_cfar_params' ranges: 1 <= train <= 64, guard >= 0, 2 (guard + train) + 1 <= fft_len.  VOTE: 0 */
+  int32_t reserved[3];                /* 0 */
+  float alpha;                        /* SOFT: > 0, finite.  VOTE: 0 */
+  float weight[CRN_MAX_FUSE_MEMBERS]; /* w_m >= 0, finite; entries at m >= group_size must be 0 */
+} crn_fuse_params; /* 168 bytes */
+typedef struct crn_fuse_row {
+  int32_t n_detected, n_any, n_all, n_active;
+} crn_fuse_row; /* 16 bytes */
+
+/* Enqueue the fusion on `stream`, one launch (device pointers):
+ *   d_bin_mask        [n_epochs][fft_len / 32]        the members' masks (8-byte aligned); NULL under SOFT: n_any = n_all = 0
+ *   d_spectrum        [n_epochs][fft_len]             the members' `spectrum` rows (16-byte aligned); NULL under VOTE: no fused row
+ *   d_fused_mask      [n_epochs / M][fft_len / 32]    or NULL (8-byte aligned)
+ *   d_fused_spectrum  [n_epochs / M][fft_len]         or NULL (16-byte aligned; refused without d_spectrum)
+ *   d_rows            [n_epochs / M]                  or NULL (16-byte aligned)
+ * `h` supplies fft_len and the device, nothing else: the arrays may come from any source, the handle may be of any mode.  Only
+ * enqueues; allocates nothing, keeps no state, needs no workspace.  CRN_ERR_ARG, decided before any device call, for a NULL h or
+ * params; all three outputs NULL; rule outside 0..1; group_size outside 1..32; epochs_per_stream < 1, or group_size epochs_per_stream
+ * not dividing n_epochs; n_epochs < 0; a negative or non-finite weight; a nonzero weight at m >= group_size; no active member; a
+ * nonzero reserved field; VOTE: NULL d_bin_mask, votes outside 1..n_active, or a nonzero guard, train or alpha; SOFT: NULL d_spectrum,
+ * votes != 0, or guard, train or alpha outside the ranges above; d_fused_spectrum without d_spectrum; a misaligned pointer.
+ * n_epochs = 0 succeeds and launches nothing. */
+CRN_API int crn_fuse_device(crn_handle *h, const uint32_t *d_bin_mask, const float *d_spectrum, int64_t n_epochs,
+                            const crn_fuse_params *params, uint32_t *d_fused_mask, float *d_fused_spectrum, crn_fuse_row *d_rows,
+                            void *stream);
+
+/* The per-sensor false-alarm probability p at which votes-of-n voting of independent sensors gives pfa_fused, host only:
+ *   sum over j = k .. n of C(n, j) p^j (1 - p)^(n - j) = pfa_fused, solved by bisection in double.
+ * The result goes into crn_cfar_alpha(p, K, W).  CRN_ERR_ARG for n outside 1..32, k outside 1..n, pfa_fused outside (0, 1) or a NULL
+ * pfa_member. */
+CRN_API int crn_fuse_member_pfa(double pfa_fused, int32_t n, int32_t k, double *pfa_member);
+
 /* Allocate, now, the device scratch and pinned staging that crn_sense_run_host needs for up to
  * max_epochs dense epochs of full-length frames (and their per-bin spectra when want_spectrum != 0),
  * and load the kernels: a later crn_sense_run_host within that size allocates nothing.  An engine

@@ -49,6 +49,7 @@ EXPORTS = [
     "crn_segments_device", "crn_tracks_workspace_bytes", "crn_tracks_device",
     "crn_tracks_carry_bytes", "crn_tracks_carry_workspace_bytes", "crn_tracks_carry_device",
     "crn_channels_workspace_bytes", "crn_channels_device", "crn_channel_forecast",
+    "crn_fuse_device", "crn_fuse_member_pfa",
     "crn_comm_unique_id", "crn_comm_create", "crn_comm_local", "crn_comm_allgather", "crn_comm_gathered",
     "crn_comm_finish", "crn_comm_destroy", "crn_comm_local_addr", "crn_comm_wait", "crn_comm_info",
     "crn_last_error", "crn_abi_version", "crn_build_info",
@@ -156,6 +157,23 @@ class ChannelStats(C.Structure):
 CHANNEL_STATS_DTYPE = [("n_epochs", "<i8"), ("n_busy", "<i8"), ("n_trans", "<i8", (2, 2)), ("n_runs", "<i8", (2,)), ("run_sum", "<i8", (2,)),
                        ("run_max", "<i8", (2,)), ("run", "<i8"), ("state", "<i4"), ("reserved", "<i4"), ("power", "<f8", (2,)),
                        ("idle_hist", "<i4", (16,))]
+CRN_MAX_FUSE_MEMBERS = 32
+FUSE_VOTE, FUSE_SOFT = 0, 1                   # crn_fuse_rule
+
+
+class FuseParams(C.Structure):
+    """crn_fuse_params (crn_fuse_device), 168 bytes."""
+    _fields_ = [("rule", C.c_int32), ("group_size", C.c_int32), ("epochs_per_stream", C.c_int32), ("votes", C.c_int32), ("guard", C.c_int32),
+                ("train", C.c_int32), ("reserved", C.c_int32 * 3), ("alpha", C.c_float), ("weight", C.c_float * CRN_MAX_FUSE_MEMBERS)]
+
+
+class FuseRow(C.Structure):
+    """crn_fuse_row: one fused row's header, 16 bytes."""
+    _fields_ = [("n_detected", C.c_int32), ("n_any", C.c_int32), ("n_all", C.c_int32), ("n_active", C.c_int32)]
+
+
+# numpy view of the headers crn_fuse_device writes: np.frombuffer(bytes, FUSE_ROW_DTYPE), one per fused row
+FUSE_ROW_DTYPE = [("n_detected", "<i4"), ("n_any", "<i4"), ("n_all", "<i4"), ("n_active", "<i4")]
 CFAR_METHODS = {"ca": CFAR_CA, "go": CFAR_GO, "so": CFAR_SO, "os": CFAR_OS}
 
 
@@ -284,6 +302,9 @@ def lib():
         L.crn_channels_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(ChannelParams), C.c_void_p, C.c_void_p, C.c_void_p,
                                           C.c_void_p, C.c_int64, C.c_void_p]
         L.crn_channel_forecast.argtypes = [C.c_void_p, C.c_int32, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]
+        L.crn_fuse_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(FuseParams), C.c_void_p, C.c_void_p, C.c_void_p,
+                                      C.c_void_p]
+        L.crn_fuse_member_pfa.argtypes = [C.c_double, C.c_int32, C.c_int32, C.POINTER(C.c_double)]
         L.crn_ingest_create.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]
         L.crn_ingest_push.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
         L.crn_ingest_flush.argtypes = [C.c_void_p]
@@ -467,6 +488,29 @@ def channels_workspace_bytes(n_epochs, spans, epochs_per_stream=None, min_bins=1
     if nb <= 0:
         raise CrnError(f"crn_channels_workspace_bytes: arguments out of range ({nb})")
     return nb
+
+
+def fuse_params(rule, group_size, epochs_per_stream, votes=0, guard=0, train=0, alpha=0.0, weights=None):
+    """crn_fuse_params: rule FUSE_VOTE (votes = k of the active members) or FUSE_SOFT (guard, train, alpha: CA-CFAR on the fused row, alpha
+    from cfar_alpha(pfa, n_active * K, train)); weights one per member, 0 = the member is left out, None = equal gain, 1 / group_size."""
+    m = int(group_size)
+    if weights is None:
+        weights = [1.0 / m] * m if 1 <= m <= CRN_MAX_FUSE_MEMBERS else []
+    if len(weights) > CRN_MAX_FUSE_MEMBERS:
+        raise ValueError(f"at most {CRN_MAX_FUSE_MEMBERS} members, not {len(weights)}")
+    q = FuseParams(rule=int(rule), group_size=m, epochs_per_stream=int(epochs_per_stream), votes=int(votes), guard=int(guard), train=int(train),
+                   alpha=float(alpha))
+    for i, w in enumerate(weights):
+        q.weight[i] = float(w)
+    return q
+
+
+def fuse_member_pfa(pfa, n, k):
+    """The per-sensor false-alarm probability at which k-of-n voting of independent sensors gives `pfa` (crn_fuse_member_pfa); it goes into
+    cfar_alpha(p, K, train)."""
+    p = C.c_double()
+    check(lib().crn_fuse_member_pfa(float(pfa), int(n), int(k), C.byref(p)), "crn_fuse_member_pfa")
+    return p.value
 
 
 def channel_spans_from_bands(cfg):
@@ -750,6 +794,14 @@ class Sensor:
         v = lambda ptr: C.c_void_p(ptr or None)      # noqa: E731
         check(lib().crn_channels_device(self._h, v(mask_ptr), v(spectrum_ptr), n_epochs, C.byref(q), v(stats_ptr), v(busy_ptr), v(power_ptr),
                                         v(workspace_ptr), int(workspace_bytes), v(stream)), "crn_channels_device")
+
+    def fuse_device(self, mask_ptr, spectrum_ptr, n_epochs, params, fused_mask_ptr=0, fused_spectrum_ptr=0, rows_ptr=0, stream=0):
+        """Fuses groups of params.group_size streams (fuse_params; device pointers): mask_ptr [n_epochs][fft_len / 32] uint32 and
+        spectrum_ptr [n_epochs][fft_len] float32, either 0 where the rule does not need it; fused_mask_ptr and fused_spectrum_ptr the same
+        shapes with n_epochs / group_size rows, rows_ptr [n_epochs / group_size] FUSE_ROW_DTYPE, each or 0.  Only enqueues."""
+        v = lambda ptr: C.c_void_p(ptr or None)      # noqa: E731
+        check(lib().crn_fuse_device(self._h, v(mask_ptr), v(spectrum_ptr), n_epochs, C.byref(params), v(fused_mask_ptr), v(fused_spectrum_ptr),
+                                    v(rows_ptr), v(stream)), "crn_fuse_device")
 
     def set_wire_full_scale(self, full_scale):
         _need_sc16("set_wire_full_scale")
