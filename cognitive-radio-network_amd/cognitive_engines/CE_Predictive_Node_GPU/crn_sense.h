@@ -595,6 +595,76 @@ CRN_API int crn_fuse_device(crn_handle *h, const uint32_t *d_bin_mask, const flo
  * pfa_member. */
 CRN_API int crn_fuse_member_pfa(double pfa_fused, int32_t n, int32_t k, double *pfa_member);
 
+/* -- spectrum holes: which parts of the band are free now, how wide, for how long, how quiet -----------------------------------
+ * crn_channels_device answers for spans the caller named in advance.  This stage answers for a user bound to no channel plan: the
+ * maximal spans whose every bin has been clear for at least min_age epochs, the latest included (the intersection of the idle bins
+ * over time, not their union).  A batch is laid out as for crn_tracks_device: n_epochs = S T, S streams of T = epochs_per_stream
+ * epochs in time order; N = fft_len; bins are circular.  d_t[k] is bit k of epoch t's mask.
+ *   1. blocked   b_t[k] = OR of d_t[(k + i) mod N] over |i| <= guard: a circular dilation of the epoch's mask.
+ *   2. age       one int32 per stream and bin in the caller's d_age [S][N], its own carry; it holds values only, no index is ever
+ *                read from it.  a = first ? 0 : max(d_age[k], 0); then for each epoch of the stream in time order
+ *                a = b_t[k] ? 0 : min(a + 1, 2^31 - 1); the result is written back.  Equivalently: when the bin was blocked in the
+ *                batch and the last such epoch is t*, a = T - 1 - t*; otherwise a = min(a_start + T, 2^31 - 1).  It is the number of
+ *                consecutive epochs, ending with the latest, in which the bin was clear, left-censored at the first call.
+ *   3. free      f[k] = age[k] >= min_age.  free_bins counts them before any width filter; d_free_mask [S][N / 32] has the bit
+ *                layout of the bin mask.
+ *   4. holes     the maximal circular runs of ones in f: bins (lo + i) mod N, 0 <= i < width.  f all ones: one hole, lo = 0,
+ *                width = N; f all zero: none.  Runs with width < min_width are dropped, n_found counts the rest, the first
+ *                min(n_found, max_holes) by ascending lo are stored (n_stored): a hole that crosses the wrap comes last.  Slots
+ *                beyond n_stored are zero-filled.  widest_lo, widest_width and widest_age (that hole's `age`) describe the widest of
+ *                all found holes, stored or not; ties go to the smallest lo; all three are 0 when there is none.
+ *   5. fields    per stored hole, age is the smallest and age_max the largest age[k] inside it.  With d_spectrum,
+ *                A = min(avg_epochs, T) and Pbar[k] = fl32(S_k / (double)A), S_k the fp64 sum of (double)P_t[k] over
+ *                t = T - A .. T - 1 in ascending t; peak_bin is the absolute bin of the largest Pbar in the hole (ties: the smallest
+ *                i) and peak_power that value; power = the sum of Pbar over the hole, accumulated in fp64 and rounded to fp32 once
+ *                (direct: no bin outside the hole enters it); floor_mean = the fp64 sum of Pbar over all free bins divided by
+ *                free_bins, rounded once, 0 when there are none.  Without d_spectrum power = peak_power = floor_mean = 0 and
+ *                peak_bin = lo.
+ *   6. cuts      a stream given in one call, and the same stream cut into several calls (first = 1, then 0), give identical d_age,
+ *                d_free_mask and integer fields; the fields that come from Pbar (power, peak_power, floor_mean, and peak_bin with
+ *                them) too when the last call of each cut has T >= avg_epochs, so that Pbar is the mean of the same rows. */
+typedef struct crn_hole_params {
+  int32_t epochs_per_stream; /* >= 1, divides n_epochs */
+  int32_t first;             /* != 0: d_age's contents mean nothing, start afresh */
+  int32_t guard;             /* 0..32: a detected bin also blocks its `guard` neighbours on each side */
+  int32_t min_age;           /* 1..2^31-1: epochs a bin must have been idle, the latest included */
+  int32_t min_width;         /* 1..fft_len */
+  int32_t max_holes;         /* 1..256 */
+  int32_t avg_epochs;        /* 1..64: rows averaged for the power fields */
+  int32_t reserved;          /* 0 */
+} crn_hole_params; /* 32 bytes */
+typedef struct crn_hole {
+  int32_t lo, width, age, age_max, peak_bin, reserved;
+  float power, peak_power;
+} crn_hole; /* 32 bytes */
+typedef struct crn_hole_stream {
+  int32_t n_found, n_stored, free_bins, widest_lo, widest_width, widest_age;
+  float floor_mean;
+  int32_t reserved;
+} crn_hole_stream; /* 32 bytes */
+
+/* Bytes of device scratch crn_holes_device needs for n_epochs epochs under `params`: needs no handle and no device (it is sized for
+ * the largest fft_len).  Positive for valid arguments (also for n_epochs = 0), -1 for a NULL params, n_epochs < 0, epochs_per_stream
+ * < 1 or not dividing n_epochs, guard outside 0..32, min_age < 1, min_width outside 1 .. the largest fft_len, max_holes outside
+ * 1..256, avg_epochs outside 1..64, or a nonzero reserved. */
+CRN_API int64_t crn_holes_workspace_bytes(int64_t n_epochs, const crn_hole_params *params);
+
+/* Enqueue the stage on `stream`, two launches (device pointers):
+ *   d_bin_mask   [n_epochs][fft_len / 32]      as crn_sense_run_device_cfar writes it (8-byte aligned)
+ *   d_spectrum   [n_epochs][fft_len]           the `spectrum` output of the same launch (16-byte aligned), or NULL
+ *   d_age        [n_streams][fft_len] int32    the carry (16-byte aligned): read (unless first != 0), then rewritten
+ *   d_streams    [n_streams]                   the headers (16-byte aligned)
+ *   d_holes      [n_streams][max_holes]        or NULL: headers only (16-byte aligned)
+ *   d_free_mask  [n_streams][fft_len / 32]     or NULL (8-byte aligned)
+ *   d_workspace  workspace_bytes >= crn_holes_workspace_bytes of scratch (8-byte aligned); its contents before and after mean nothing
+ * `h` supplies fft_len and the device, nothing else.  Only enqueues, allocates nothing, keeps no host state.  CRN_ERR_ARG, decided
+ * before any device call, for a NULL h, params, d_bin_mask, d_age, d_streams or d_workspace; n_epochs < 0; any parameter outside the
+ * ranges above (min_width against the handle's fft_len); a nonzero reserved; a misaligned pointer; a workspace too small.
+ * n_epochs = 0 succeeds and launches nothing, with first != 0 too (d_age is then left as it is). */
+CRN_API int crn_holes_device(crn_handle *h, const uint32_t *d_bin_mask, const float *d_spectrum, int64_t n_epochs,
+                             const crn_hole_params *params, int32_t *d_age, crn_hole_stream *d_streams, crn_hole *d_holes,
+                             uint32_t *d_free_mask, void *d_workspace, int64_t workspace_bytes, void *stream);
+
 /* Allocate, now, the device scratch and pinned staging that crn_sense_run_host needs for up to
  * max_epochs dense epochs of full-length frames (and their per-bin spectra when want_spectrum != 0),
  * and load the kernels: a later crn_sense_run_host within that size allocates nothing.  An engine

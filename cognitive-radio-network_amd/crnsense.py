@@ -50,6 +50,7 @@ EXPORTS = [
     "crn_tracks_carry_bytes", "crn_tracks_carry_workspace_bytes", "crn_tracks_carry_device",
     "crn_channels_workspace_bytes", "crn_channels_device", "crn_channel_forecast",
     "crn_fuse_device", "crn_fuse_member_pfa",
+    "crn_holes_workspace_bytes", "crn_holes_device",
     "crn_comm_unique_id", "crn_comm_create", "crn_comm_local", "crn_comm_allgather", "crn_comm_gathered",
     "crn_comm_finish", "crn_comm_destroy", "crn_comm_local_addr", "crn_comm_wait", "crn_comm_info",
     "crn_last_error", "crn_abi_version", "crn_build_info",
@@ -174,6 +175,31 @@ class FuseRow(C.Structure):
 
 # numpy view of the headers crn_fuse_device writes: np.frombuffer(bytes, FUSE_ROW_DTYPE), one per fused row
 FUSE_ROW_DTYPE = [("n_detected", "<i4"), ("n_any", "<i4"), ("n_all", "<i4"), ("n_active", "<i4")]
+
+
+class HoleParams(C.Structure):
+    """crn_hole_params (crn_holes_device), 32 bytes."""
+    _fields_ = [("epochs_per_stream", C.c_int32), ("first", C.c_int32), ("guard", C.c_int32), ("min_age", C.c_int32), ("min_width", C.c_int32),
+                ("max_holes", C.c_int32), ("avg_epochs", C.c_int32), ("reserved", C.c_int32)]
+
+
+class Hole(C.Structure):
+    """crn_hole: one stored hole, bins (lo + i) mod fft_len, 0 <= i < width; 32 bytes."""
+    _fields_ = [("lo", C.c_int32), ("width", C.c_int32), ("age", C.c_int32), ("age_max", C.c_int32), ("peak_bin", C.c_int32),
+                ("reserved", C.c_int32), ("power", C.c_float), ("peak_power", C.c_float)]
+
+
+class HoleStream(C.Structure):
+    """crn_hole_stream: one stream's header, 32 bytes."""
+    _fields_ = [("n_found", C.c_int32), ("n_stored", C.c_int32), ("free_bins", C.c_int32), ("widest_lo", C.c_int32), ("widest_width", C.c_int32),
+                ("widest_age", C.c_int32), ("floor_mean", C.c_float), ("reserved", C.c_int32)]
+
+
+# numpy views of what crn_holes_device writes: (.., HOLE_STREAM_DTYPE) [n_streams] and (.., HOLE_DTYPE) [n_streams][max_holes]
+HOLE_DTYPE = [("lo", "<i4"), ("width", "<i4"), ("age", "<i4"), ("age_max", "<i4"), ("peak_bin", "<i4"), ("reserved", "<i4"), ("power", "<f4"),
+              ("peak_power", "<f4")]
+HOLE_STREAM_DTYPE = [("n_found", "<i4"), ("n_stored", "<i4"), ("free_bins", "<i4"), ("widest_lo", "<i4"), ("widest_width", "<i4"),
+                     ("widest_age", "<i4"), ("floor_mean", "<f4"), ("reserved", "<i4")]
 CFAR_METHODS = {"ca": CFAR_CA, "go": CFAR_GO, "so": CFAR_SO, "os": CFAR_OS}
 
 
@@ -305,6 +331,9 @@ def lib():
         L.crn_fuse_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(FuseParams), C.c_void_p, C.c_void_p, C.c_void_p,
                                       C.c_void_p]
         L.crn_fuse_member_pfa.argtypes = [C.c_double, C.c_int32, C.c_int32, C.POINTER(C.c_double)]
+        L.crn_holes_workspace_bytes.argtypes, L.crn_holes_workspace_bytes.restype = [C.c_int64, C.POINTER(HoleParams)], C.c_int64
+        L.crn_holes_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(HoleParams), C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
         L.crn_ingest_create.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]
         L.crn_ingest_push.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
         L.crn_ingest_flush.argtypes = [C.c_void_p]
@@ -511,6 +540,42 @@ def fuse_member_pfa(pfa, n, k):
     p = C.c_double()
     check(lib().crn_fuse_member_pfa(float(pfa), int(n), int(k), C.byref(p)), "crn_fuse_member_pfa")
     return p.value
+
+
+def hole_params(epochs_per_stream, guard=0, min_age=1, min_width=1, max_holes=16, avg_epochs=1, first=False):
+    """crn_hole_params."""
+    return HoleParams(epochs_per_stream=int(epochs_per_stream), first=int(bool(first)), guard=int(guard), min_age=int(min_age),
+                      min_width=int(min_width), max_holes=int(max_holes), avg_epochs=int(avg_epochs), reserved=0)
+
+
+def holes_workspace_bytes(n_epochs, epochs_per_stream=None, guard=0, min_age=1, min_width=1, max_holes=16, avg_epochs=1):
+    """Bytes of device scratch Sensor.holes_device needs (crn_holes_workspace_bytes): no handle, no device."""
+    q = hole_params(n_epochs if epochs_per_stream is None else epochs_per_stream, guard, min_age, min_width, max_holes, avg_epochs)
+    nb = lib().crn_holes_workspace_bytes(int(n_epochs), C.byref(q))
+    if nb <= 0:
+        raise CrnError(f"crn_holes_workspace_bytes: arguments out of range ({nb})")
+    return nb
+
+
+def hole_hz(lo, width, fft_len, fs, fc):
+    """(centre frequency, bandwidth) in Hz of a hole from crn_holes_device: the centre is the geometric one, at bin lo + (width - 1) / 2,
+    and the mapping of bins to hertz is segment_hz's, so a hole that crosses the wrap (lo + width > N) comes out around fc."""
+    return segment_hz(lo, width, (float(width) - 1.0) / 2.0, fft_len, fs, fc)
+
+
+def pick_hole(holes, need_bins):
+    """The index of the stored hole to transmit in: among the holes of one stream (records of HOLE_DTYPE; slots with width 0 are empty) with
+    width >= need_bins, the one idle longest (the largest `age`); ties go to the lower power per bin, then to the lower lo.  None when
+    none fits."""
+    best = None
+    for i, h in enumerate(holes):
+        w = int(h["width"])
+        if w < 1 or w < need_bins:
+            continue
+        key = (-int(h["age"]), float(h["power"]) / w, int(h["lo"]), i)
+        if best is None or key < best:
+            best = key
+    return None if best is None else best[3]
 
 
 def channel_spans_from_bands(cfg):
@@ -794,6 +859,17 @@ class Sensor:
         v = lambda ptr: C.c_void_p(ptr or None)      # noqa: E731
         check(lib().crn_channels_device(self._h, v(mask_ptr), v(spectrum_ptr), n_epochs, C.byref(q), v(stats_ptr), v(busy_ptr), v(power_ptr),
                                         v(workspace_ptr), int(workspace_bytes), v(stream)), "crn_channels_device")
+
+    def holes_device(self, mask_ptr, spectrum_ptr, n_epochs, age_ptr, streams_ptr, workspace_ptr, workspace_bytes, params, holes_ptr=0,
+                     free_mask_ptr=0, stream=0):
+        """Spectrum holes with idle age from n_epochs rows of a CFAR bin mask and, unless spectrum_ptr is 0, the matching `spectrum` rows
+        (device pointers; params from hole_params): age_ptr [n_streams][fft_len] int32, the carry, read (unless params.first) and
+        rewritten; streams_ptr [n_streams] HOLE_STREAM_DTYPE; holes_ptr [n_streams][params.max_holes] HOLE_DTYPE or 0; free_mask_ptr
+        [n_streams][fft_len / 32] uint32 or 0; workspace_ptr at least holes_workspace_bytes(...) of scratch;
+        n_streams = n_epochs / params.epochs_per_stream.  Only enqueues."""
+        v = lambda ptr: C.c_void_p(ptr or None)      # noqa: E731
+        check(lib().crn_holes_device(self._h, v(mask_ptr), v(spectrum_ptr), n_epochs, C.byref(params), v(age_ptr), v(streams_ptr), v(holes_ptr),
+                                     v(free_mask_ptr), v(workspace_ptr), int(workspace_bytes), v(stream)), "crn_holes_device")
 
     def fuse_device(self, mask_ptr, spectrum_ptr, n_epochs, params, fused_mask_ptr=0, fused_spectrum_ptr=0, rows_ptr=0, stream=0):
         """Fuses groups of params.group_size streams (fuse_params; device pointers): mask_ptr [n_epochs][fft_len / 32] uint32 and
