@@ -2,7 +2,7 @@
 // CFAR bit mask and, optionally, the `spectrum` rows of a batch become one record per stream and channel that the caller carries from
 // call to call.  Three small launches on the caller's stream, all scratch in the caller's workspace:
 //
-//   1. epoch  channels_epoch_kernel<B>, one wave per epoch, the lane-owns-B-bins mapping of segments_kernel<B> (crn_segments.hip): the
+//   1. epoch  channels_epoch_kernel<B>, one wave per epoch, the lane-owns-B-bins mapping of segments_kernel<B> (crn_mask_runs.h): the
 //             row is read once with coalesced float4 loads into LDS (padded by 4 floats per lane piece), the mask piece sits in a
 //             register.  Lane l sums its own B bins once (fp64) and leaves that sum and its mask piece in LDS.  Then lane c owns
 //             channel c: it walks the pieces the span touches, at most two of them partly (bin by bin, only bins inside the span) and
@@ -28,14 +28,13 @@
 #include <string>
 
 #include "crn_internal.h"
+#include "crn_mask_runs.h"
 #include "crn_segments.h"
 
 namespace crn {
 namespace {
 
-constexpr int MAX_N = 4096;      // the largest fft_len: what a span is held to where no handle says more
-constexpr int CHUNK = 64;        // epochs per time summary: one bit each of a lane's time word
-constexpr int JOIN_WAVES = 8;
+constexpr int JOIN_WAVES = 8;    // (a time summary is over CHUNK = 64 epochs: one bit each of a lane's time word)
 
 struct ChanParams {
   const uint32_t *mask;     // [n_epochs][N / 32]
@@ -47,13 +46,10 @@ struct ChanParams {
   crn_channel_span span[CRN_MAX_CHANNELS];
 };
 
-__device__ __forceinline__ uint64_t low_bits(int n) { return n >= 64 ? ~0ull : (1ull << n) - 1; }
-
 template <int B>
 __global__ __launch_bounds__(64) void channels_epoch_kernel(const ChanParams p) {
   constexpr int N = 64 * B;
-  constexpr int PAD = 4;   // floats between lane pieces in LDS, as in segments_kernel
-  __shared__ float4 row4[(N + 64 * PAD) / 4];
+  __shared__ float4 row4[padded_words(B) / 4];
   __shared__ double piece_sum[64];
   __shared__ uint64_t piece_mask[64];
   float *row = reinterpret_cast<float *>(row4);
@@ -61,30 +57,13 @@ __global__ __launch_bounds__(64) void channels_epoch_kernel(const ChanParams p) 
   const long long e = p.first + blockIdx.x;
   const bool spec = p.spectrum != nullptr;
 
-  if (spec) {
-    const float4 *src = reinterpret_cast<const float4 *>(p.spectrum + e * N);
-#pragma unroll
-    for (int j = 0; j < B / 4; j++) {
-      const int k = 4 * (j * 64 + l);
-      *reinterpret_cast<float4 *>(row + k + (k / B) * PAD) = src[j * 64 + l];
-    }
-  }
-  const uint32_t *mw = p.mask + e * (N / 32);
-  uint64_t d;
-  if (B == 64) {
-    const uint2 w = reinterpret_cast<const uint2 *>(mw)[l];
-    d = (uint64_t)w.x | ((uint64_t)w.y << 32);
-  } else if (B == 32) {
-    d = mw[l];
-  } else {
-    d = (mw[l / (32 / B)] >> ((l % (32 / B)) * B)) & ((1ull << (B % 64)) - 1);
-  }
-  piece_mask[l] = d;
+  if (spec) load_row<B>(row, p.spectrum + e * N, l);
+  piece_mask[l] = mask_piece<B>(p.mask + e * (N / 32), l);
   __syncthreads();
 
   // the lane's own bins, once
   if (spec) {
-    const float *mine = row + l * (B + PAD);
+    const float *mine = own_piece<B>(row, l);
     double w = 0.0;
 #pragma unroll
     for (int i4 = 0; i4 < B; i4 += 4) {
@@ -114,7 +93,7 @@ __global__ __launch_bounds__(64) void channels_epoch_kernel(const ChanParams p) 
       } else {
         nd += __popcll(piece_mask[r] & low_bits(pe - q * B) & ~low_bits(pos - q * B));
         if (spec) {
-          const float *theirs = row + r * (B + PAD) - q * B;
+          const float *theirs = own_piece<B>(row, r) - q * B;
           for (int k = pos; k < pe; k++) s += (double)theirs[k];
         }
       }
@@ -253,10 +232,9 @@ __device__ __forceinline__ TimeSum sum_load(const int *at, int nch, uint64_t *hi
 __global__ __launch_bounds__(64) void channels_time_kernel(const TimeParams p) {
   const int l = threadIdx.x;
   const long long chunk = p.first + blockIdx.x;
-  const long long stream = chunk / p.chunks;
-  const int t0 = (int)(chunk - stream * p.chunks) * CHUNK;
-  const int n = p.eps - t0 < CHUNK ? p.eps - t0 : CHUNK;          // 1..64 epochs
-  const long long e0 = stream * p.eps + t0;
+  const ChunkSpan cs = chunk_span(chunk, p.chunks, p.eps);
+  const int n = cs.n;
+  const long long e0 = cs.stream * p.eps + cs.t0;
   const uint64_t w = l < n ? p.busy[e0 + l] : 0;
   uint64_t x = 0;                                                  // bit i: this lane's channel busy in epoch e0 + i
   for (int c = 0; c < p.nch; c++) {
@@ -464,7 +442,7 @@ struct Layout {
 };
 Layout layout_of(int64_t n_epochs, const crn_channel_params &q) {
   Layout y;
-  y.chunks = (int64_t(q.epochs_per_stream) + CHUNK - 1) / CHUNK;   // 64-bit: epochs_per_stream may be close to 2^31
+  y.chunks = chunks_per_stream(q.epochs_per_stream);
   const int64_t n_streams = n_epochs / q.epochs_per_stream;
   y.busy = 0;
   y.power = n_epochs * 8;
@@ -475,7 +453,6 @@ Layout layout_of(int64_t n_epochs, const crn_channel_params &q) {
 }
 
 inline int refuse(const char *why) { return fail(CRN_ERR_ARG, std::string("crn_channels_device: ") + why); }
-inline bool misaligned(const void *ptr, uintptr_t a) { return (reinterpret_cast<uintptr_t>(ptr) & (a - 1)) != 0; }
 
 template <int B>
 hipError_t launch_epochs(const ChanParams &p, unsigned n, hipStream_t stream) {
@@ -510,7 +487,6 @@ int crn_channels_device(crn_handle *h, const uint32_t *d_bin_mask, const float *
   char *ws = static_cast<char *>(d_workspace);
   hipError_t err = hipSetDevice(device);
   hipStream_t st = static_cast<hipStream_t>(stream);
-  const int64_t grid = int64_t(1) << 30;   // workgroups per launch: one launch of each kernel for any batch that fits a device
   crn::ChanParams p;
   p.mask = d_bin_mask;
   p.spectrum = d_spectrum;
@@ -519,28 +495,25 @@ int crn_channels_device(crn_handle *h, const uint32_t *d_bin_mask, const float *
   p.nch = params->n_channels;
   p.min_bins = params->min_bins;
   for (int c = 0; c < CRN_MAX_CHANNELS; c++) p.span[c] = c < p.nch ? params->span[c] : crn_channel_span{0, 1};
-  for (int64_t first = 0; err == hipSuccess && first < n_epochs; first += grid) {
+  err = crn::in_grids(err, n_epochs, [&](int64_t first, unsigned cnt) {
     p.first = first;
-    const unsigned cnt = (unsigned)(n_epochs - first < grid ? n_epochs - first : grid);
-    err = n == 512 ? crn::launch_epochs<8>(p, cnt, st) : n == 1024 ? crn::launch_epochs<16>(p, cnt, st)
-          : n == 2048 ? crn::launch_epochs<32>(p, cnt, st) : crn::launch_epochs<64>(p, cnt, st);
-  }
+    return n == 512 ? crn::launch_epochs<8>(p, cnt, st) : n == 1024 ? crn::launch_epochs<16>(p, cnt, st)
+           : n == 2048 ? crn::launch_epochs<32>(p, cnt, st) : crn::launch_epochs<64>(p, cnt, st);
+  });
   const int64_t n_streams = n_epochs / params->epochs_per_stream;
   crn::TimeParams t{p.busy, p.power, reinterpret_cast<int *>(ws + y.sums), d_stats, 0, p.nch, params->epochs_per_stream, (int)y.chunks,
                     params->first != 0};
-  for (int64_t first = 0; err == hipSuccess && first < n_streams * y.chunks; first += grid) {
+  err = crn::in_grids(err, n_streams * y.chunks, [&](int64_t first, unsigned cnt) {
     t.first = first;
-    const unsigned cnt = (unsigned)(n_streams * y.chunks - first < grid ? n_streams * y.chunks - first : grid);
     hipLaunchKernelGGL(crn::channels_time_kernel, dim3(cnt), dim3(64), 0, st, t);
-    err = hipGetLastError();
-  }
+    return hipGetLastError();
+  });
   const int waves = y.chunks < crn::JOIN_WAVES ? (int)y.chunks : crn::JOIN_WAVES;
-  for (int64_t first = 0; err == hipSuccess && first < n_streams; first += grid) {
+  err = crn::in_grids(err, n_streams, [&](int64_t first, unsigned cnt) {
     t.first = first;
-    const unsigned cnt = (unsigned)(n_streams - first < grid ? n_streams - first : grid);
     hipLaunchKernelGGL(crn::channels_join_kernel, dim3(cnt), dim3(64 * waves), 0, st, t);
-    err = hipGetLastError();
-  }
+    return hipGetLastError();
+  });
   if (err != hipSuccess) return crn::fail(CRN_ERR_DEVICE, std::string("crn_channels_device: ") + hipGetErrorString(err));
   return CRN_OK;
 }

@@ -160,7 +160,6 @@ __global__ __launch_bounds__(TPB) void fuse_kernel(const FuseParams p) {
 }
 
 inline int refuse(const char *why) { return fail(CRN_ERR_ARG, std::string("crn_fuse_device: ") + why); }
-inline bool misaligned(const void *ptr, uintptr_t a) { return (reinterpret_cast<uintptr_t>(ptr) & (a - 1)) != 0; }
 
 template <int N, int TPB>
 hipError_t launch(const FuseParams &p, unsigned n, hipStream_t stream) {
@@ -241,13 +240,11 @@ int crn_fuse_device(crn_handle *h, const uint32_t *d_bin_mask, const float *d_sp
   hipError_t err = hipSetDevice(device);
   hipStream_t st = static_cast<hipStream_t>(stream);
   const int64_t n_rows = n_epochs / q.group_size;
-  const int64_t grid = int64_t(1) << 30;   // workgroups per launch: one launch for any batch that fits a device
-  for (int64_t first = 0; err == hipSuccess && first < n_rows; first += grid) {
+  err = crn::in_grids(err, n_rows, [&](int64_t first, unsigned cnt) {
     p.first = first;
-    const unsigned cnt = (unsigned)(n_rows - first < grid ? n_rows - first : grid);
-    err = n == 512 ? crn::launch<512, 128>(p, cnt, st) : n == 1024 ? crn::launch<1024, 256>(p, cnt, st)
-          : n == 2048 ? crn::launch<2048, 256>(p, cnt, st) : crn::launch<4096, 256>(p, cnt, st);
-  }
+    return n == 512 ? crn::launch<512, 128>(p, cnt, st) : n == 1024 ? crn::launch<1024, 256>(p, cnt, st)
+           : n == 2048 ? crn::launch<2048, 256>(p, cnt, st) : crn::launch<4096, 256>(p, cnt, st);
+  });
   if (err != hipSuccess) return crn::fail(CRN_ERR_DEVICE, std::string("crn_fuse_device: ") + hipGetErrorString(err));
   return CRN_OK;
 }

@@ -12,9 +12,9 @@
 //               from the latest backwards, 16 rows in flight, until its wave has every bin resolved or the chunks are exhausted: a
 //               stream of T epochs is at most T / 1024 dependent steps and as a rule one or two.  The result is combined with d_age under
 //               the saturating rule; d_age and the free mask are written; ages and Pbar (the fp64 mean of the last A rows, coalesced
-//               float4 loads) go to LDS, each lane piece padded by 4 words.  Wave 0 then extracts the runs in the manner of
-//               segments_kernel<B> (crn_segments.hip): lane l owns the B bins [l B, (l + 1) B), slots come from the bits alone (an
-//               add scan over lanes), one walk over the lane's bins, and a segmented circular scan joins the lanes.
+//               float4 loads) go to LDS, each lane piece padded by 4 words.  Wave 0 then extracts the runs with what it shares with
+//               segments_kernel<B> (crn_mask_runs.h): lane l owns the B bins [l B, (l + 1) B), slots come from the bits alone
+//               (run_plan<B>), one walk over the lane's bins with this unit's own accumulator, and join_spanning joins the lanes.
 // Every value read from d_age or from the workspace is used as a value, never as an index.  Sums are fp64 and direct (no bin outside a
 // hole enters its sum), rounded to fp32 once.  No scratch memory, no global atomics, plain vector stores.
 #include <hip/hip_runtime.h>
@@ -23,14 +23,13 @@
 #include <string>
 
 #include "crn_internal.h"
+#include "crn_mask_runs.h"
 #include "crn_segments.h"
 
 namespace crn {
 namespace {
 
-constexpr int MAX_N = 4096;      // the largest fft_len: what min_width and the workspace are held to where no handle says more
-constexpr int CHUNK = 64;        // epochs per row of the workspace
-constexpr int IN_FLIGHT = 16;    // chunk rows the stream kernel loads before it looks at any
+constexpr int IN_FLIGHT = 16;    // chunk rows (CHUNK epochs each) the stream kernel loads before it looks at any
 constexpr int32_t AGE_MAX = 0x7fffffff;
 
 struct LastParams {
@@ -40,45 +39,15 @@ struct LastParams {
   int eps, chunks, guard;
 };
 
-// the small bit helpers of crn_segments.hip (copies: that unit stays as it is)
-__device__ __forceinline__ int ctz64(uint64_t x) { return x ? __builtin_ctzll(x) : 64; }
-__device__ __forceinline__ int clz64(uint64_t x) { return x ? __builtin_clzll(x) : 64; }
-__device__ __forceinline__ uint64_t rotl64(uint64_t x, int r) { return r ? (x << r) | (x >> (64 - r)) : x; }
-__device__ __forceinline__ uint64_t low_bits(int n) { return n >= 64 ? ~0ull : (1ull << n) - 1; }
-// bit x of the result = OR (AND) of bits x - i (x + i) of the argument, 0 <= i <= g <= 63; zeros come in at the ends
-__device__ __forceinline__ uint64_t or_up(uint64_t x, int g) {
-  int c = 1;
-  for (; 2 * c <= g + 1; c *= 2) x |= x << c;
-  return x | (x << (g + 1 - c));
-}
-__device__ __forceinline__ uint64_t or_down(uint64_t x, int g) {
-  int c = 1;
-  for (; 2 * c <= g + 1; c *= 2) x |= x >> c;
-  return x | (x >> (g + 1 - c));
-}
-__device__ __forceinline__ uint64_t and_down(uint64_t x, int g) {
-  int c = 1;
-  for (; 2 * c <= g + 1; c *= 2) x &= x >> c;
-  return x & (x >> (g + 1 - c));
-}
-
-// the word `cur` dilated by g <= 32 bins, `prev` and `next` its neighbours in the circular row
-__device__ __forceinline__ uint32_t dilate(uint32_t prev, uint32_t cur, uint32_t next, int g) {
-  const uint64_t below = (uint64_t)prev | ((uint64_t)cur << 32), above = (uint64_t)cur | ((uint64_t)next << 32);
-  return (uint32_t)(or_up(below, g) >> 32) | (uint32_t)or_down(above, g);
-}
-
 template <int N>
 __global__ __launch_bounds__(N / 8) void holes_last_kernel(const LastParams p) {
   constexpr int W = N / 32, TH = N / 8;
   __shared__ uint32_t blocked[CHUNK * W];
   const int tid = threadIdx.x;
   const long long chunk = p.first + blockIdx.x;
-  const long long stream = chunk / p.chunks;
-  const int t0 = (int)(chunk - stream * p.chunks) * CHUNK;
-  const int n = p.eps - t0 < CHUNK ? p.eps - t0 : CHUNK;          // 1..64 epochs
-  const uint32_t *rows = p.mask + (stream * p.eps + t0) * W;
-  for (int i = tid; i < n * W; i += TH) {
+  const ChunkSpan cs = chunk_span(chunk, p.chunks, p.eps);
+  const uint32_t *rows = p.mask + (cs.stream * p.eps + cs.t0) * W;
+  for (int i = tid; i < cs.n * W; i += TH) {
     const int w = i & (W - 1), r = i - w;
     const uint32_t cur = rows[i];
     blocked[i] = p.guard == 0 ? cur : dilate(rows[r + ((w - 1) & (W - 1))], cur, rows[r + ((w + 1) & (W - 1))], p.guard);
@@ -89,7 +58,7 @@ __global__ __launch_bounds__(N / 8) void holes_last_kernel(const LastParams p) {
   const int sh = 8 * (tid & 3);
   uint32_t lo = 0xffffffffu, hi = 0xffffffffu;                    // one byte per bin: the last blocked epoch of the chunk so far
 #pragma unroll 4
-  for (int t = 0; t < n; t++) {
+  for (int t = 0; t < cs.n; t++) {
     const uint32_t x = col[t * W] >> sh;
     // bits 0..3 to the low bits of four bytes (the four shifted copies do not overlap), then to whole bytes (m * 0xFF as a shift and a subtraction)
     const uint32_t blo = ((x & 15) * 0x00204081u) & 0x01010101u, bhi = (((x >> 4) & 15) * 0x00204081u) & 0x01010101u;
@@ -150,10 +119,8 @@ __global__ __launch_bounds__(B == 8 ? 128 : 256) void holes_stream_kernel(const 
   constexpr int N = 64 * B;
   constexpr int TH = B == 8 ? 128 : 256;     // threads
   constexpr int G = N / 4 / TH;              // groups of 4 bins per thread: group q = j TH + tid is bins 4 q .. 4 q + 3
-  constexpr int PAD = 4;                     // words between lane pieces in LDS, as in segments_kernel
-  constexpr uint64_t PM = B == 64 ? ~0ull : (1ull << (B % 64)) - 1;
-  __shared__ float4 row4[(N + 64 * PAD) / 4];   // Pbar
-  __shared__ int4 age4[(N + 64 * PAD) / 4];
+  __shared__ float4 row4[padded_words(B) / 4];  // Pbar
+  __shared__ int4 age4[padded_words(B) / 4];
   __shared__ uint32_t fw[N / 32];               // the free mask
   float *row = reinterpret_cast<float *>(row4);
   int *ages = reinterpret_cast<int *>(age4);
@@ -228,8 +195,7 @@ __global__ __launch_bounds__(B == 8 ? 128 : 256) void holes_stream_kernel(const 
     }
     const int4 now = make_int4(a[j][0], a[j][1], a[j][2], a[j][3]);
     *at = now;
-    const int k = 4 * q;
-    *reinterpret_cast<int4 *>(ages + k + (k / B) * PAD) = now;
+    *reinterpret_cast<int4 *>(padded<B>(ages, 4 * q)) = now;
     // eight neighbouring lanes hold one word of the free mask
     f <<= 4 * (tid & 7);
     f |= __shfl_xor(f, 1, 64);
@@ -261,51 +227,17 @@ __global__ __launch_bounds__(B == 8 ? 128 : 256) void holes_stream_kernel(const 
       const double d = (double)A;
       mean = make_float4((float)(s0 / d), (float)(s1 / d), (float)(s2 / d), (float)(s3 / d));
     }
-    const int k = 4 * q;
-    *reinterpret_cast<float4 *>(row + k + (k / B) * PAD) = mean;
+    *reinterpret_cast<float4 *>(padded<B>(row, 4 * q)) = mean;
   }
   __syncthreads();
   if (tid >= 64) return;
 
   // wave 0: lane l owns the bins [l B, (l + 1) B) and its piece of the free mask
   const int l = tid;
-  uint64_t c;
-  if (B == 64) {
-    c = (uint64_t)fw[2 * l] | ((uint64_t)fw[2 * l + 1] << 32);
-  } else if (B == 32) {
-    c = fw[l];
-  } else {
-    c = (fw[l / (32 / B)] >> ((l % (32 / B)) * B)) & PM;
-  }
+  const uint64_t c = mask_piece<B>(fw, l);
 
-  // run structure from the bits.  An all-ones circle is cut between lane 63 and lane 0: one hole, lo = 0, width = N.
-  const bool all_ones = __ballot(c == PM) == ~0ull;
-  const uint64_t tops = __ballot((c >> (B - 1)) & 1), lows = __ballot(c & 1);
-  const bool cont_in = (c & 1) && ((tops >> ((l - 1) & 63)) & 1) && !(all_ones && l == 0);
-  const bool cont_out = ((c >> (B - 1)) & 1) && ((lows >> ((l + 1) & 63)) & 1) && !(all_ones && l == 63);
-  const bool pass = c == PM && cont_in && cont_out;          // a lane in the middle of a hole
-  const int headlen = cont_in ? ctz64(~c & PM) < B ? ctz64(~c & PM) : B : 0;
-  const int taillen = cont_out ? (clz64(~(c << (64 - B))) < B ? clz64(~(c << (64 - B))) : B) : 0;
-  // the bins a hole has gathered before it enters this lane: whole lanes back to the nearest lane that is not `pass`, and its tail
-  const uint64_t pt = __ballot(pass);
-  const int dist_s = clz64(rotl64(~pt, (64 - l) & 63));
-  const int carry_w = dist_s * B + __shfl(taillen, (l - 1 - dist_s) & 63, 64);
-  const bool head_final = cont_in && !pass;                  // a hole from an earlier lane ends here
-  const int head_w = carry_w + headlen;
-  const int head_lo = l * B + headlen - head_w;              // < 0: it crosses the wrap
-  const bool head_kept = head_final && head_w >= p.min_width;
-  const uint64_t own = c & ~low_bits(headlen) & low_bits(B - taillen);   // runs that start and end in this lane
-  const uint64_t er = p.min_width - 1 >= B ? 0 : and_down(own, p.min_width - 1);
-  const int cnt = __popcll(er & ~(er << 1)) + (head_kept ? 1 : 0);
-  int incl = cnt;
-#pragma unroll
-  for (int s = 1; s < 64; s *= 2) {
-    const int y = __shfl_up(incl, s, 64);
-    if (l >= s) incl += y;
-  }
-  const int n_found = __shfl(incl, 63, 64);
-  const int n_stored = n_found < p.max_holes ? n_found : p.max_holes;
-  const bool wrap_kept = __ballot(head_kept && head_lo < 0) != 0;   // that hole ends first (rank 0) and is stored last
+  // run structure from the bits
+  const RunPlan plan = run_plan<B>(c, l, p.min_width, p.max_holes);
   crn_hole *holes = p.holes ? p.holes + stream * p.max_holes : nullptr;
   int best_w = 0, best_lo = 0, best_age = 0;                 // the widest hole this lane has emitted, stored or not
 
@@ -315,7 +247,7 @@ __global__ __launch_bounds__(B == 8 ? 128 : 256) void holes_stream_kernel(const 
       best_lo = lo;
       best_age = s.amin;
     }
-    const int slot = wrap_kept ? (rank == 0 ? n_found - 1 : rank - 1) : rank;
+    const int slot = plan.slot(rank);
     if (holes == nullptr || slot >= p.max_holes) return;
     crn_hole o;
     o.lo = lo;
@@ -332,8 +264,8 @@ __global__ __launch_bounds__(B == 8 ? 128 : 256) void holes_stream_kernel(const 
   // one walk over the lane's bins
   Acc r = acc_zero(), head = acc_zero();
   double fsum = 0.0;
-  int rank = incl - cnt + (head_kept ? 1 : 0);
-  bool in_head = cont_in;
+  int rank = plan.incl - plan.cnt + (plan.head_kept ? 1 : 0);
+  bool in_head = plan.cont_in;
   auto close_run = [&](int end) {
     if (in_head) {
       head = r;
@@ -344,8 +276,8 @@ __global__ __launch_bounds__(B == 8 ? 128 : 256) void holes_stream_kernel(const 
     r = acc_zero();
     in_head = false;
   };
-  const float *mine = row + l * (B + PAD);
-  const int *mine_age = ages + l * (B + PAD);
+  const float *mine = own_piece<B>(row, l);
+  const int *mine_age = own_piece<B>(ages, l);
 #pragma unroll 1
   for (int i4 = 0; i4 < B; i4 += 4) {
     const float4 qp = *reinterpret_cast<const float4 *>(mine + i4);
@@ -371,22 +303,11 @@ __global__ __launch_bounds__(B == 8 ? 128 : 256) void holes_stream_kernel(const 
       }
     }
   }
-  if (r.w && !cont_out) close_run(B);
+  if (r.w && !plan.cont_out) close_run(B);
 
-  // spanning holes: v = what leaves this lane through its high edge, joined back to the lane where the hole started
-  Acc v = cont_out ? r : acc_zero();
-  bool done = !pass;
-#pragma unroll
-  for (int s = 1; s < 64; s *= 2) {
-    const Acc o = acc_from(v, (l - s) & 63);
-    const bool o_done = __shfl((int)done, (l - s) & 63, 64) != 0;
-    if (!done) {
-      v = acc_join(o, v);
-      done = o_done;
-    }
-  }
-  const Acc carry = acc_from(v, (l - 1) & 63);
-  if (head_kept) emit(acc_join(carry, head), head_lo < 0 ? head_lo + N : head_lo, incl - cnt);
+  // spanning holes: what leaves this lane through its high edge is joined back to the lane where the hole started
+  const Acc carry = join_spanning(plan.cont_out ? r : acc_zero(), plan.pass, l);
+  if (plan.head_kept) emit(acc_join(carry, head), plan.head_lo < 0 ? plan.head_lo + N : plan.head_lo, plan.incl - plan.cnt);
 
   // the stream's header, and zeros in the slots nobody filled
   int nfree = __popcll(c);
@@ -403,8 +324,8 @@ __global__ __launch_bounds__(B == 8 ? 128 : 256) void holes_stream_kernel(const 
   }
   if (l == 0) {
     crn_hole_stream h;
-    h.n_found = n_found;
-    h.n_stored = n_stored;
+    h.n_found = plan.n_found;
+    h.n_stored = plan.n_stored;
     h.free_bins = nfree;
     h.widest_lo = best_lo;
     h.widest_width = best_w;
@@ -415,7 +336,7 @@ __global__ __launch_bounds__(B == 8 ? 128 : 256) void holes_stream_kernel(const 
   }
   if (holes != nullptr) {
     crn_hole z{};
-    for (int s = n_stored + l; s < p.max_holes; s += 64) holes[s] = z;
+    for (int s = plan.n_stored + l; s < p.max_holes; s += 64) holes[s] = z;
   }
 }
 
@@ -434,16 +355,13 @@ const char *hole_params_refusal(const crn_hole_params &q, int64_t n_epochs, int 
   return nullptr;
 }
 
-int64_t chunks_of(const crn_hole_params &q) { return (int64_t(q.epochs_per_stream) + CHUNK - 1) / CHUNK; }   // 64-bit: close to 2^31
-
 // the workspace: one byte per bin and (stream, chunk), rows of n bytes
 int64_t workspace_of(int64_t n_epochs, const crn_hole_params &q, int n) {
-  const int64_t bytes = n_epochs / q.epochs_per_stream * chunks_of(q) * n;
+  const int64_t bytes = n_epochs / q.epochs_per_stream * chunks_per_stream(q.epochs_per_stream) * n;
   return bytes < 64 ? 64 : bytes;
 }
 
 inline int refuse(const char *why) { return fail(CRN_ERR_ARG, std::string("crn_holes_device: ") + why); }
-inline bool misaligned(const void *ptr, uintptr_t a) { return (reinterpret_cast<uintptr_t>(ptr) & (a - 1)) != 0; }
 
 template <int N>
 hipError_t launch_last(const LastParams &p, unsigned n, hipStream_t stream) {
@@ -482,23 +400,20 @@ int crn_holes_device(crn_handle *h, const uint32_t *d_bin_mask, const float *d_s
 
   hipError_t err = hipSetDevice(device);
   hipStream_t st = static_cast<hipStream_t>(stream);
-  const int64_t grid = int64_t(1) << 30;   // workgroups per launch: one launch of each kernel for any batch that fits a device
-  const int64_t chunks = crn::chunks_of(*params), n_streams = n_epochs / params->epochs_per_stream;
+  const int64_t chunks = crn::chunks_per_stream(params->epochs_per_stream), n_streams = n_epochs / params->epochs_per_stream;
   crn::LastParams lp{d_bin_mask, static_cast<uint8_t *>(d_workspace), 0, params->epochs_per_stream, (int)chunks, params->guard};
-  for (int64_t first = 0; err == hipSuccess && first < n_streams * chunks; first += grid) {
+  err = crn::in_grids(err, n_streams * chunks, [&](int64_t first, unsigned cnt) {
     lp.first = first;
-    const unsigned cnt = (unsigned)(n_streams * chunks - first < grid ? n_streams * chunks - first : grid);
-    err = n == 512 ? crn::launch_last<512>(lp, cnt, st) : n == 1024 ? crn::launch_last<1024>(lp, cnt, st)
-          : n == 2048 ? crn::launch_last<2048>(lp, cnt, st) : crn::launch_last<4096>(lp, cnt, st);
-  }
+    return n == 512 ? crn::launch_last<512>(lp, cnt, st) : n == 1024 ? crn::launch_last<1024>(lp, cnt, st)
+           : n == 2048 ? crn::launch_last<2048>(lp, cnt, st) : crn::launch_last<4096>(lp, cnt, st);
+  });
   crn::StreamParams sp{lp.last, d_spectrum, d_age, d_streams, d_holes, d_free_mask, 0, params->epochs_per_stream, (int)chunks,
                        params->first != 0, params->min_age, params->min_width, params->max_holes, params->avg_epochs};
-  for (int64_t first = 0; err == hipSuccess && first < n_streams; first += grid) {
+  err = crn::in_grids(err, n_streams, [&](int64_t first, unsigned cnt) {
     sp.first = first;
-    const unsigned cnt = (unsigned)(n_streams - first < grid ? n_streams - first : grid);
-    err = n == 512 ? crn::launch_streams<8>(sp, cnt, st) : n == 1024 ? crn::launch_streams<16>(sp, cnt, st)
-          : n == 2048 ? crn::launch_streams<32>(sp, cnt, st) : crn::launch_streams<64>(sp, cnt, st);
-  }
+    return n == 512 ? crn::launch_streams<8>(sp, cnt, st) : n == 1024 ? crn::launch_streams<16>(sp, cnt, st)
+           : n == 2048 ? crn::launch_streams<32>(sp, cnt, st) : crn::launch_streams<64>(sp, cnt, st);
+  });
   if (err != hipSuccess) return crn::fail(CRN_ERR_DEVICE, std::string("crn_holes_device: ") + hipGetErrorString(err));
   return CRN_OK;
 }

@@ -7,14 +7,13 @@
 //   1. the row is read once with coalesced float4 loads into LDS (padded by 4 floats per lane piece), the mask once from HBM;
 //   2. closing is bit arithmetic on the piece (dilate by merge_gap, erode by merge_gap); the two zero runs that touch the piece's
 //      edges are decided with the neighbouring non-empty lanes' trailing / leading zero counts, found with one __ballot and one __shfl;
-//   3. the number of segments that END in each lane and survive min_width comes from the bits alone (an erosion by min_width - 1 and a
-//      popcount of run starts), so an inclusive add scan over the wave gives every segment its slot before any power is summed.
-//      Segments are disjoint, so ascending end equals ascending lo except for the one segment that crosses the wrap: it ends first and
-//      is stored last;
+//   3. the number of segments that END in each lane and survive min_width comes from the bits alone, so an add scan over the wave gives
+//      every segment its slot before any power is summed; the segment that crosses the wrap ends first and is stored last (run_plan<B>);
 //   4. each lane walks its B bins once (LDS reads), emitting the segments that start and end inside it and keeping the run that
 //      touches its low edge (head) and the one that leaves through its high edge (tail);
-//   5. a segmented scan over lanes (6 steps, circular) joins tail + whole lanes, and the lane where a spanning segment ends adds its
-//      head and emits it.
+//   5. a segmented circular scan over lanes joins tail + whole lanes (join_spanning); the lane where a spanning segment ends adds its head.
+// The mapping of 1, the bit helpers, 3 and 5 are in crn_mask_runs.h: the spectrum holes (crn_holes.hip) run them over an accumulator of
+// their own, the channel statistics (crn_channels.hip) use the mapping.
 // Sums are fp64 and offsets are relative to the segment's own lo at every join (no cancellation), rounded to fp32 once.
 // A lane never walks more than its own B <= 64 bins, whatever the mask holds; no atomics, no scratch, plain vector stores.
 #include <hip/hip_runtime.h>
@@ -23,6 +22,7 @@
 #include <string>
 
 #include "crn_internal.h"
+#include "crn_mask_runs.h"
 #include "crn_segments.h"
 
 namespace crn {
@@ -70,56 +70,18 @@ __device__ __forceinline__ Acc acc_from(const Acc &a, int lane) {
   return r;
 }
 
-__device__ __forceinline__ int ctz64(uint64_t x) { return x ? __builtin_ctzll(x) : 64; }
-__device__ __forceinline__ int clz64(uint64_t x) { return x ? __builtin_clzll(x) : 64; }
-__device__ __forceinline__ uint64_t rotl64(uint64_t x, int r) { return r ? (x << r) | (x >> (64 - r)) : x; }
-__device__ __forceinline__ uint64_t rotr64(uint64_t x, int r) { return r ? (x >> r) | (x << (64 - r)) : x; }
-__device__ __forceinline__ uint64_t low_bits(int n) { return n >= 64 ? ~0ull : (1ull << n) - 1; }
-
-// bit x of the result = OR (AND) of bits x - i (x + i) of the argument, 0 <= i <= g <= 63; zeros come in at the ends
-__device__ __forceinline__ uint64_t or_up(uint64_t x, int g) {
-  int c = 1;
-  for (; 2 * c <= g + 1; c *= 2) x |= x << c;
-  return x | (x << (g + 1 - c));
-}
-__device__ __forceinline__ uint64_t or_down(uint64_t x, int g) {
-  int c = 1;
-  for (; 2 * c <= g + 1; c *= 2) x |= x >> c;
-  return x | (x >> (g + 1 - c));
-}
-__device__ __forceinline__ uint64_t and_down(uint64_t x, int g) {
-  int c = 1;
-  for (; 2 * c <= g + 1; c *= 2) x &= x >> c;
-  return x & (x >> (g + 1 - c));
-}
-
 template <int B>
 __global__ __launch_bounds__(64) void segments_kernel(const SegParams p) {
   constexpr int N = 64 * B;
-  constexpr int PAD = 4;                     // floats between lane pieces in LDS: a lane's float4 reads then spread over the banks
-  constexpr uint64_t PM = B == 64 ? ~0ull : (1ull << (B % 64)) - 1;
-  __shared__ float4 row4[(N + 64 * PAD) / 4];
+  constexpr uint64_t PM = piece_bits(B);
+  __shared__ float4 row4[padded_words(B) / 4];
   float *row = reinterpret_cast<float *>(row4);
   const int l = threadIdx.x;
   const long long e = p.first + blockIdx.x;
 
-  // 1. the row: coalesced from HBM, to the lane that owns the bins through LDS
-  const float4 *src = reinterpret_cast<const float4 *>(p.spectrum + e * N);
-#pragma unroll
-  for (int j = 0; j < B / 4; j++) {
-    const int k = 4 * (j * 64 + l);
-    *reinterpret_cast<float4 *>(row + k + (k / B) * PAD) = src[j * 64 + l];
-  }
-  const uint32_t *mw = p.mask + e * (N / 32);
-  uint64_t d;
-  if (B == 64) {
-    const uint2 w = reinterpret_cast<const uint2 *>(mw)[l];
-    d = (uint64_t)w.x | ((uint64_t)w.y << 32);
-  } else if (B == 32) {
-    d = mw[l];
-  } else {
-    d = (mw[l / (32 / B)] >> ((l % (32 / B)) * B)) & PM;
-  }
+  // 1. the row: coalesced from HBM, to the lane that owns the bins through LDS; the lane's piece of the mask
+  load_row<B>(row, p.spectrum + e * N, l);
+  const uint64_t d = mask_piece<B>(p.mask + e * (N / 32), l);
 
   // 2. closing
   const int g = p.merge_gap;
@@ -144,38 +106,12 @@ __global__ __launch_bounds__(64) void segments_kernel(const SegParams p) {
     }
   }
 
-  // 3. run structure from the bits.  An all-ones circle is cut between lane 63 and lane 0: one segment, lo = 0, width = N.
-  const bool all_ones = __ballot(c == PM) == ~0ull;
-  const uint64_t tops = __ballot((c >> (B - 1)) & 1), lows = __ballot(c & 1);
-  const bool cont_in = (c & 1) && ((tops >> ((l - 1) & 63)) & 1) && !(all_ones && l == 0);
-  const bool cont_out = ((c >> (B - 1)) & 1) && ((lows >> ((l + 1) & 63)) & 1) && !(all_ones && l == 63);
-  const bool pass = c == PM && cont_in && cont_out;          // a lane in the middle of a segment
-  const int headlen = cont_in ? ctz64(~c & PM) < B ? ctz64(~c & PM) : B : 0;
-  const int taillen = cont_out ? (clz64(~(c << (64 - B))) < B ? clz64(~(c << (64 - B))) : B) : 0;
-  // the bins a segment has gathered before it enters this lane: whole lanes back to the nearest lane that is not `pass`, and its tail
-  const uint64_t pt = __ballot(pass);
-  const int dist_s = clz64(rotl64(~pt, (64 - l) & 63));
-  const int carry_w = dist_s * B + __shfl(taillen, (l - 1 - dist_s) & 63, 64);
-  const bool head_final = cont_in && !pass;                  // a segment from an earlier lane ends here
-  const int head_w = carry_w + headlen;
-  const int head_lo = l * B + headlen - head_w;              // < 0: it crosses the wrap
-  const bool head_kept = head_final && head_w >= p.min_width;
-  const uint64_t own = c & ~low_bits(headlen) & low_bits(B - taillen);   // runs that start and end in this lane
-  const uint64_t er = p.min_width - 1 >= B ? 0 : and_down(own, p.min_width - 1);
-  const int cnt = __popcll(er & ~(er << 1)) + (head_kept ? 1 : 0);
-  int incl = cnt;
-#pragma unroll
-  for (int s = 1; s < 64; s *= 2) {
-    const int y = __shfl_up(incl, s, 64);
-    if (l >= s) incl += y;
-  }
-  const int n_found = __shfl(incl, 63, 64);
-  const int n_stored = n_found < p.max_segments ? n_found : p.max_segments;
-  const bool wrap_kept = __ballot(head_kept && head_lo < 0) != 0;   // that segment ends first (rank 0) and is stored last
+  // 3. run structure from the bits
+  const RunPlan plan = run_plan<B>(c, l, p.min_width, p.max_segments);
   crn_segment *segs = p.segments ? p.segments + e * p.max_segments : nullptr;
 
   auto emit = [&](const Acc &s, int lo, int rank) {
-    const int slot = wrap_kept ? (rank == 0 ? n_found - 1 : rank - 1) : rank;
+    const int slot = plan.slot(rank);
     if (segs == nullptr || slot >= p.max_segments) return;
     crn_segment o;
     o.lo = lo;
@@ -193,8 +129,8 @@ __global__ __launch_bounds__(64) void segments_kernel(const SegParams p) {
   __syncthreads();
   Acc a = acc_zero(), head = acc_zero();
   double nsum = 0.0;
-  int rank = incl - cnt + (head_kept ? 1 : 0);
-  bool in_head = cont_in;
+  int rank = plan.incl - plan.cnt + (plan.head_kept ? 1 : 0);
+  bool in_head = plan.cont_in;
   auto close_run = [&](int end) {
     if (in_head) {
       head = a;
@@ -205,7 +141,7 @@ __global__ __launch_bounds__(64) void segments_kernel(const SegParams p) {
     a = acc_zero();
     in_head = false;
   };
-  const float *mine = row + l * (B + PAD);
+  const float *mine = own_piece<B>(row, l);
 #pragma unroll 1
   for (int i4 = 0; i4 < B; i4 += 4) {
     const float4 q = *reinterpret_cast<const float4 *>(mine + i4);
@@ -229,22 +165,11 @@ __global__ __launch_bounds__(64) void segments_kernel(const SegParams p) {
       }
     }
   }
-  if (a.w && !cont_out) close_run(B);
+  if (a.w && !plan.cont_out) close_run(B);
 
-  // 5. spanning segments: v = what leaves this lane through its high edge, joined back to the lane where the segment started
-  Acc v = cont_out ? a : acc_zero();
-  bool done = !pass;
-#pragma unroll
-  for (int s = 1; s < 64; s *= 2) {
-    const Acc o = acc_from(v, (l - s) & 63);
-    const bool o_done = __shfl((int)done, (l - s) & 63, 64) != 0;
-    if (!done) {
-      v = acc_join(o, v);
-      done = o_done;
-    }
-  }
-  const Acc carry = acc_from(v, (l - 1) & 63);
-  if (head_kept) emit(acc_join(carry, head), head_lo < 0 ? head_lo + N : head_lo, incl - cnt);
+  // 5. spanning segments: what leaves this lane through its high edge is joined back to the lane where the segment started
+  const Acc carry = join_spanning(plan.cont_out ? a : acc_zero(), plan.pass, l);
+  if (plan.head_kept) emit(acc_join(carry, head), plan.head_lo < 0 ? plan.head_lo + N : plan.head_lo, plan.incl - plan.cnt);
 
   // the epoch's header, and zeros in the slots nobody filled
   int nbins = B - __popcll(c);
@@ -255,15 +180,15 @@ __global__ __launch_bounds__(64) void segments_kernel(const SegParams p) {
   }
   if (l == 0) {
     crn_segment_epoch h;
-    h.n_found = n_found;
-    h.n_stored = n_stored;
+    h.n_found = plan.n_found;
+    h.n_stored = plan.n_stored;
     h.noise_bins = nbins;
     h.noise_mean = nbins ? (float)(nsum / (double)nbins) : 0.0f;
     p.epochs[e] = h;
   }
   if (segs != nullptr) {
     crn_segment z{};
-    for (int s = n_stored + l; s < p.max_segments; s += 64) segs[s] = z;
+    for (int s = plan.n_stored + l; s < p.max_segments; s += 64) segs[s] = z;
   }
 }
 
@@ -294,12 +219,10 @@ int crn_segments_device(crn_handle *h, const uint32_t *d_bin_mask, const float *
   hipError_t err = hipSetDevice(device);
   hipStream_t st = static_cast<hipStream_t>(stream);
   crn::SegParams p{d_bin_mask, d_spectrum, d_epochs, d_segments, 0, params->merge_gap, params->min_width, params->max_segments};
-  const int64_t chunk = int64_t(1) << 30;   // workgroups per grid: one launch for any batch that fits a device
-  for (int64_t first = 0; err == hipSuccess && first < n_epochs; first += chunk) {
+  err = crn::in_grids(err, n_epochs, [&](int64_t first, unsigned cnt) {
     p.first = first;
-    const unsigned cnt = (unsigned)(n_epochs - first < chunk ? n_epochs - first : chunk);
-    err = n == 512 ? crn::launch<8>(p, cnt, st) : n == 1024 ? crn::launch<16>(p, cnt, st) : n == 2048 ? crn::launch<32>(p, cnt, st) : crn::launch<64>(p, cnt, st);
-  }
+    return n == 512 ? crn::launch<8>(p, cnt, st) : n == 1024 ? crn::launch<16>(p, cnt, st) : n == 2048 ? crn::launch<32>(p, cnt, st) : crn::launch<64>(p, cnt, st);
+  });
   if (err != hipSuccess) return crn::fail(CRN_ERR_DEVICE, std::string("crn_segments_device: ") + hipGetErrorString(err));
   return CRN_OK;
 }

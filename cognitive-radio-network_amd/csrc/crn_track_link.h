@@ -14,6 +14,7 @@
 #include <string>
 
 #include "crn_internal.h"
+#include "crn_segments.h"
 
 namespace crn {
 
@@ -136,11 +137,10 @@ inline const char *track_params_refusal(const crn_track_params &q, int64_t n_epo
   return nullptr;
 }
 
-// the entry points' bookkeeping: CRN_ERR_ARG / CRN_ERR_DEVICE as "<who>: <why>", a pointer's alignment, the workspace from its first
-// 64-byte boundary on
+// the entry points' bookkeeping: CRN_ERR_ARG / CRN_ERR_DEVICE as "<who>: <why>", the workspace from its first 64-byte boundary on (a
+// pointer's alignment: misaligned, crn_segments.h)
 inline int refuse(const char *who, const char *why) { return fail(CRN_ERR_ARG, std::string(who) + ": " + why); }
 inline int fail_hip(const char *who, hipError_t err) { return fail(CRN_ERR_DEVICE, std::string(who) + ": " + hipGetErrorString(err)); }
-inline bool misaligned(const void *ptr, uintptr_t a) { return (reinterpret_cast<uintptr_t>(ptr) & (a - 1)) != 0; }
 inline char *align64(void *ptr) { return reinterpret_cast<char *>((reinterpret_cast<uintptr_t>(ptr) + 63) & ~uintptr_t(63)); }
 
 }  // namespace crn
