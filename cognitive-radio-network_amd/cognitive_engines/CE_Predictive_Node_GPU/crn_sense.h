@@ -665,6 +665,68 @@ CRN_API int crn_holes_device(crn_handle *h, const uint32_t *d_bin_mask, const fl
                              const crn_hole_params *params, int32_t *d_age, crn_hole_stream *d_streams, crn_hole *d_holes,
                              uint32_t *d_free_mask, void *d_workspace, int64_t workspace_bytes, void *stream);
 
+/* -- wideband detection against an excised noise floor (LAD, localisation by double thresholding) -------------------------------
+ * The CFAR detectors compare a bin with its neighbours and are blind to an emitter wider than the training window: its interior
+ * bins have the emitter on both sides.  This stage finds the noise floor of the row itself by forward consecutive mean excision
+ * (FCME), thresholds every bin against it, and accepts a run of bins over a lower threshold only where it holds a bin over an upper
+ * one.  Per epoch, no state, no calibrated noise power.  Its output has the layout of the CFAR mask, so every stage above takes it.
+ * One row is P[0..N), N = fft_len, the `spectrum` output of one epoch; the values are taken as non-negative finite fp32 (for a row
+ * that holds anything else that row's outputs are unspecified, and nothing outside them is touched).  The row is cut into n_blocks
+ * blocks of M = N / n_blocks >= 256 bins, block b the bins [b M, (b + 1) M), each with a floor of its own (the receiver's floor is
+ * not flat: filter roll-off).
+ *   1. floor       x_(1) <= .. <= x_(M) the block's values ascending, C_n = sum of (double)x_(i) over i <= n,
+ *                  n0 = max(1, M init_percent / 100) (integer division).  n* is the smallest n in n0 .. M with n == M or
+ *                  (double)x_(n+1) n > (double)t_cme C_n.  floor_b = C_n* / n* in fp64; d_floor[row][b] is that rounded to fp32 once.
+ *   2. thresholds  lower[k]  <=>  (double)P[k] n* > (double)t_lower C_n*, with n* and C_n* of k's block; upper[k] the same with
+ *                  t_upper.  t_lower <= t_upper: upper is a subset of lower.
+ *   3. clusters    the maximal circular runs of ones in `lower` (lower all ones: one cluster of width N).  A cluster is kept when
+ *                  it holds at least one `upper` bin; det is the union of the kept clusters.  A cluster may cross block edges and
+ *                  the wrap.
+ *   4. output      out = det | or_mask, or_mask an optional input in the mask layout (the CFAR mask of the same launch, so that
+ *                  one mask carries both detectors); it may be the same address as d_bin_mask.
+ *   5. header      n_lower, n_upper: the set bits of lower and upper; n_detected: the set bits of out; n_clusters: kept clusters;
+ *                  n_rejected: clusters without an upper bin; n_clean: the sum of n* over the blocks; floor_min, floor_max: the
+ *                  smallest and the largest d_floor of the row.
+ *   6. arithmetic  the fp64 sums may be added in any order.  A row is decided when every comparison of steps 1-2 that the
+ *                  ascending-order evaluation makes has |lhs / rhs - 1| > 2^-36 (or both sides 0); decided rows have exactly the
+ *                  outputs of that evaluation (x n is exact in fp64, and C_n in another order moves by at most M 2^-53 relative).
+ *   Limits         the floor needs noise to stand on: a block that an emitter fills, or a row occupied beyond about 80 %, puts the
+ *                  floor on the emitter.  Rows are independent: a batch gives the same bytes however it is cut. */
+typedef struct crn_lad_params {
+  int32_t n_blocks;       /* 1, 2, 4, 8; fft_len / n_blocks >= 256 */
+  int32_t init_percent;   /* 1..50: the share of a block taken as surely noise */
+  float t_cme;            /* > 0, finite: crn_lad_factor(pfa_cme, K, 0) */
+  float t_lower, t_upper; /* > 0, finite, t_lower <= t_upper: crn_lad_factor(pfa, K, t_cme) */
+  int32_t reserved[3];    /* 0 */
+} crn_lad_params; /* 32 bytes */
+typedef struct crn_lad_row {
+  int32_t n_lower, n_upper, n_detected, n_clusters, n_rejected, n_clean;
+  float floor_min, floor_max;
+} crn_lad_row; /* 32 bytes */
+
+/* Enqueue the stage on `stream`, one launch (device pointers):
+ *   d_spectrum  [n_epochs][fft_len]            `spectrum` rows (16-byte aligned)
+ *   d_or_mask   [n_epochs][fft_len / 32]       or NULL (8-byte aligned); may be d_bin_mask itself
+ *   d_bin_mask  [n_epochs][fft_len / 32]       or NULL (8-byte aligned)
+ *   d_rows      [n_epochs]                     or NULL (16-byte aligned)
+ *   d_floor     [n_epochs][n_blocks] float     or NULL (4-byte aligned)
+ * `h` supplies fft_len and the device, nothing else.  Only enqueues; allocates nothing, keeps no state, needs no workspace.
+ * CRN_ERR_ARG, decided before any device call, for a NULL h, params or d_spectrum; all three outputs NULL; n_blocks outside
+ * {1, 2, 4, 8} or fft_len / n_blocks < 256; init_percent outside 1..50; t_cme, t_lower or t_upper not finite or <= 0;
+ * t_lower > t_upper; a nonzero reserved; n_epochs < 0; a misaligned pointer.  n_epochs = 0 succeeds and launches nothing. */
+CRN_API int crn_lad_device(crn_handle *h, const float *d_spectrum, int64_t n_epochs, const crn_lad_params *params,
+                           const uint32_t *d_or_mask, uint32_t *d_bin_mask, crn_lad_row *d_rows, float *d_floor, void *stream);
+
+/* The factors of crn_lad_params from false-alarm rates, host only, under crn_cfar_alpha's noise model (P is Gamma(K), mean 1,
+ * K = frames_per_epoch):
+ *   t_cme == 0   factor = G_K^-1(1 - pfa) / K, the plain quantile: this gives t_cme itself.
+ *   t_cme > 0    that quantile divided by m, the mean FCME converges to in noise: the fixed point of
+ *                m = P(K + 1, K t_cme m) / P(K, K t_cme m), iterated from m = 1 (P the regularised lower incomplete gamma).  The
+ *                excised floor sits below the true mean, and an uncorrected threshold runs high.
+ * Blocks much smaller than 256 bins bias the floor further down (the n0 smallest of few values): hence M >= 256.
+ * CRN_ERR_ARG for pfa outside (0, 1), frames_per_epoch < 1, a negative or non-finite t_cme, or a NULL factor. */
+CRN_API int crn_lad_factor(double pfa, int32_t frames_per_epoch, double t_cme, double *factor);
+
 /* Allocate, now, the device scratch and pinned staging that crn_sense_run_host needs for up to
  * max_epochs dense epochs of full-length frames (and their per-bin spectra when want_spectrum != 0),
  * and load the kernels: a later crn_sense_run_host within that size allocates nothing.  An engine

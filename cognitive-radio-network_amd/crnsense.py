@@ -51,6 +51,7 @@ EXPORTS = [
     "crn_channels_workspace_bytes", "crn_channels_device", "crn_channel_forecast",
     "crn_fuse_device", "crn_fuse_member_pfa",
     "crn_holes_workspace_bytes", "crn_holes_device",
+    "crn_lad_device", "crn_lad_factor",
     "crn_comm_unique_id", "crn_comm_create", "crn_comm_local", "crn_comm_allgather", "crn_comm_gathered",
     "crn_comm_finish", "crn_comm_destroy", "crn_comm_local_addr", "crn_comm_wait", "crn_comm_info",
     "crn_last_error", "crn_abi_version", "crn_build_info",
@@ -200,6 +201,17 @@ HOLE_DTYPE = [("lo", "<i4"), ("width", "<i4"), ("age", "<i4"), ("age_max", "<i4"
               ("peak_power", "<f4")]
 HOLE_STREAM_DTYPE = [("n_found", "<i4"), ("n_stored", "<i4"), ("free_bins", "<i4"), ("widest_lo", "<i4"), ("widest_width", "<i4"),
                      ("widest_age", "<i4"), ("floor_mean", "<f4"), ("reserved", "<i4")]
+
+
+class LadParams(C.Structure):
+    """crn_lad_params (crn_lad_device), 32 bytes."""
+    _fields_ = [("n_blocks", C.c_int32), ("init_percent", C.c_int32), ("t_cme", C.c_float), ("t_lower", C.c_float), ("t_upper", C.c_float),
+                ("reserved", C.c_int32 * 3)]
+
+
+# numpy view of the headers crn_lad_device writes: np.frombuffer(bytes, LAD_ROW_DTYPE), one per epoch
+LAD_ROW_DTYPE = [("n_lower", "<i4"), ("n_upper", "<i4"), ("n_detected", "<i4"), ("n_clusters", "<i4"), ("n_rejected", "<i4"), ("n_clean", "<i4"),
+                 ("floor_min", "<f4"), ("floor_max", "<f4")]
 CFAR_METHODS = {"ca": CFAR_CA, "go": CFAR_GO, "so": CFAR_SO, "os": CFAR_OS}
 
 
@@ -334,6 +346,8 @@ def lib():
         L.crn_holes_workspace_bytes.argtypes, L.crn_holes_workspace_bytes.restype = [C.c_int64, C.POINTER(HoleParams)], C.c_int64
         L.crn_holes_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(HoleParams), C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+        L.crn_lad_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(LadParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.crn_lad_factor.argtypes = [C.c_double, C.c_int32, C.c_double, C.POINTER(C.c_double)]
         L.crn_ingest_create.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]
         L.crn_ingest_push.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
         L.crn_ingest_flush.argtypes = [C.c_void_p]
@@ -555,6 +569,20 @@ def holes_workspace_bytes(n_epochs, epochs_per_stream=None, guard=0, min_age=1, 
     if nb <= 0:
         raise CrnError(f"crn_holes_workspace_bytes: arguments out of range ({nb})")
     return nb
+
+
+def lad_params(n_blocks=1, init_percent=10, t_cme=0.0, t_lower=0.0, t_upper=0.0):
+    """crn_lad_params: the factors come from lad_factor, t_cme = lad_factor(pfa_cme, K) and t_lower, t_upper = lad_factor(pfa, K, t_cme)."""
+    return LadParams(n_blocks=int(n_blocks), init_percent=int(init_percent), t_cme=float(t_cme), t_lower=float(t_lower), t_upper=float(t_upper))
+
+
+def lad_factor(pfa, K, t_cme=0.0):
+    """The threshold factor over the excised floor at which a noise bin (the mean of K frames) exceeds it with probability pfa
+    (crn_lad_factor): t_cme = 0 gives the plain Gamma(K) quantile, which is the FCME factor itself; with t_cme > 0 the quantile is divided
+    by the mean the excision converges to in noise."""
+    f = C.c_double()
+    check(lib().crn_lad_factor(float(pfa), int(K), float(t_cme), C.byref(f)), "crn_lad_factor")
+    return f.value
 
 
 def hole_hz(lo, width, fft_len, fs, fc):
@@ -870,6 +898,15 @@ class Sensor:
         v = lambda ptr: C.c_void_p(ptr or None)      # noqa: E731
         check(lib().crn_holes_device(self._h, v(mask_ptr), v(spectrum_ptr), n_epochs, C.byref(params), v(age_ptr), v(streams_ptr), v(holes_ptr),
                                      v(free_mask_ptr), v(workspace_ptr), int(workspace_bytes), v(stream)), "crn_holes_device")
+
+    def lad_device(self, spectrum_ptr, n_epochs, params, mask_ptr=0, rows_ptr=0, floor_ptr=0, or_mask_ptr=0, stream=None):
+        """Wideband detection against an excised noise floor on n_epochs `spectrum` rows (device pointers; params from lad_params):
+        mask_ptr [n_epochs][fft_len / 32] uint32, the CFAR mask's layout; rows_ptr [n_epochs] LAD_ROW_DTYPE; floor_ptr
+        [n_epochs][params.n_blocks] float32; each or 0, not all three.  or_mask_ptr: a mask of the same layout OR-ed into the output (the
+        CFAR mask of the same launch; it may be mask_ptr itself), or 0.  Only enqueues."""
+        v = lambda ptr: C.c_void_p(ptr or None)      # noqa: E731
+        check(lib().crn_lad_device(self._h, v(spectrum_ptr), n_epochs, C.byref(params), v(or_mask_ptr), v(mask_ptr), v(rows_ptr), v(floor_ptr),
+                                   v(stream)), "crn_lad_device")
 
     def fuse_device(self, mask_ptr, spectrum_ptr, n_epochs, params, fused_mask_ptr=0, fused_spectrum_ptr=0, rows_ptr=0, stream=0):
         """Fuses groups of params.group_size streams (fuse_params; device pointers): mask_ptr [n_epochs][fft_len / 32] uint32 and

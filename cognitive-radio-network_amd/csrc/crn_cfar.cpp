@@ -232,3 +232,35 @@ int crn_cfar_alpha_ex(int32_t method, double pfa, int32_t frames_per_epoch, int3
   if (!solve_alpha(tail, pfa, alpha)) return crn::fail(CRN_ERR_ARG, "crn_cfar_alpha_ex: pfa too small");
   return CRN_OK;
 }
+
+int crn_lad_factor(double pfa, int32_t frames_per_epoch, double t_cme, double *factor) {
+  if (!factor) return crn::fail(CRN_ERR_ARG, "crn_lad_factor: null factor");
+  if (!(pfa > 0.0 && pfa < 1.0)) return crn::fail(CRN_ERR_ARG, "crn_lad_factor: pfa must be in (0, 1)");
+  if (frames_per_epoch < 1) return crn::fail(CRN_ERR_ARG, "crn_lad_factor: frames_per_epoch < 1");
+  if (!std::isfinite(t_cme) || t_cme < 0.0) return crn::fail(CRN_ERR_ARG, "crn_lad_factor: t_cme must be finite and >= 0");
+  // In units of the noise power P is Gamma(K) with mean 1: K P has the unit-scale Gamma(K) law, whose upper tail is Q(K, .)
+  const double K = frames_per_epoch, lgk = std::lgamma(K), lgk1 = std::lgamma(K + 1.0);
+  double q = 0.0;
+  auto tail = [&](double s) {
+    double P, Q;
+    inc_gamma(K, s, lgk, &P, &Q);
+    return Q;
+  };
+  if (!solve_alpha(tail, pfa, &q)) return crn::fail(CRN_ERR_ARG, "crn_lad_factor: pfa too small");
+  double m = 1.0;
+  if (t_cme > 0.0) {
+    // the mean of the values FCME keeps, those below t_cme times that mean: E[P; P < c] / Pr(P < c) = P(K + 1, K c) / P(K, K c)
+    for (int it = 0; it < 10000; it++) {
+      double P1, Pk, Q;
+      inc_gamma(K + 1.0, K * t_cme * m, lgk1, &P1, &Q);
+      inc_gamma(K, K * t_cme * m, lgk, &Pk, &Q);
+      const double next = P1 / Pk;
+      if (!(next > 0.0) || !std::isfinite(next)) return crn::fail(CRN_ERR_ARG, "crn_lad_factor: t_cme too small: the excised mean vanishes");
+      const bool still = std::fabs(next - m) <= 1e-16 * m;
+      m = next;
+      if (still) break;
+    }
+  }
+  *factor = q / K / m;
+  return CRN_OK;
+}
