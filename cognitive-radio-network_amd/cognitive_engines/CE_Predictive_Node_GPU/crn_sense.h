@@ -727,6 +727,70 @@ CRN_API int crn_lad_device(crn_handle *h, const float *d_spectrum, int64_t n_epo
  * CRN_ERR_ARG for pfa outside (0, 1), frames_per_epoch < 1, a negative or non-finite t_cme, or a NULL factor. */
 CRN_API int crn_lad_factor(double pfa, int32_t frames_per_epoch, double t_cme, double *factor);
 
+/* -- ordered-statistic CFAR along time, per bin (the radar "clutter-map" CFAR) -----------------------------------------------------
+ * The CFAR detectors and crn_lad_device take their noise reference from the other bins of the same row.  This stage takes it from the
+ * same bin's own past: a floor of any shape in frequency, a fixed spur and a DC spike are constant in time and therefore floor, and an
+ * emitter of any width is seen whole.  Its output has the layout of the CFAR mask, so every stage above takes it.  A batch is laid out
+ * as for crn_tracks_device: n_epochs = S T, S streams of T = epochs_per_stream epochs in time order; N = fft_len; P_n[k] is bin k of
+ * the `spectrum` row of the stream's epoch n.  Per stream, `seen` is the number of epochs given in earlier calls: 0 when first != 0,
+ * otherwise d_seen[stream] read as a value and clamped to 0 .. 2^62.  Epoch t of the call has the global index n = seen + t.
+ * D = cells, g = guard_epochs, H = D + g.
+ *   1. cells     for n >= H the cells of (n, k) are c_i = P_(n-g-i)[k], i = 1..D: the bin's own D epochs before the g guard epochs.  A
+ *                row comes from the batch where it lies inside the batch and from the history otherwise.  For n < H there are no
+ *                cells: the bin is not detected and n_cells = 0 (the warm-up).
+ *   2. test      det  <=>  at least `rank` cells satisfy fl32(alpha c_i) < P_n[k]: an fp32 product and an fp32 compare, strict, a tie
+ *                counts as "not below".  It is the counting form of CRN_CFAR_OS on K-frame means, so
+ *                crn_cfar_alpha_ex(CRN_CFAR_OS, pfa, K, cells / 2, rank) gives alpha (K-frame means of disjoint epochs are independent).
+ *   3. output    out = det | or_mask, or_mask an optional input in the mask layout (the CFAR or LAD mask of the same rows, so that
+ *                one mask carries every detector); it may be the same address as d_bin_mask.
+ *   4. header    n_detected: the set bits of out; n_new: the bits of det not in or_mask; n_cells: 0 in the warm-up, D after it.
+ *   5. history   the caller owns d_hist [S][H][N] fp32 and d_seen [S] int64.  The row of global epoch n lives in slot n mod H.  After
+ *                the call the slots of the last min(H, seen + T) epochs hold those rows and d_seen = seen + T.  Slots of epochs never
+ *                seen are never read.  No index is read from either array (n mod H is in range whatever d_seen holds): a foreign
+ *                buffer costs wrong bits and nothing else.
+ *   6. cuts      a stream given in one call, and the same stream cut anywhere into several calls (first = 1, then 0), give identical
+ *                masks, headers, d_seen and written history slots.
+ *   7. values    taken as non-negative finite fp32.  For a bin whose test value or cells hold anything else that bin's outputs are
+ *                unspecified, and nothing outside the outputs is touched.
+ *   Limits       a bin that is busy in more than D - rank of its D cells raises its own threshold, and an always-on emitter is floor:
+ *                the blind spot is the complement of the other detectors', hence the OR.  The first H epochs of a stream yield
+ *                nothing.  alpha assumes that cells and test are independent: true of disjoint epochs whatever the window, not of
+ *                Welch epochs that share fft_len - hop samples with their neighbour (guard_epochs >= 1 keeps the test clear of it;
+ *                neighbouring cells stay correlated). */
+typedef struct crn_tcfar_params {
+  int32_t epochs_per_stream; /* >= 1, divides n_epochs */
+  int32_t first;             /* != 0: d_hist's and d_seen's contents mean nothing, start afresh */
+  int32_t cells;             /* D: even, 2..128 (train = cells / 2 is within crn_cfar_alpha_ex's 1..64) */
+  int32_t guard_epochs;      /* g: 0..16 */
+  int32_t rank;              /* 1..cells */
+  float alpha;               /* > 0, finite: crn_cfar_alpha_ex(CRN_CFAR_OS, pfa, K, cells / 2, rank) */
+  int32_t reserved[2];       /* 0 */
+} crn_tcfar_params; /* 32 bytes */
+typedef struct crn_tcfar_row {
+  int32_t n_detected, n_new, n_cells, reserved;
+} crn_tcfar_row; /* 16 bytes */
+
+/* Bytes of d_hist for n_streams streams of fft_len bins under `params`, n_streams (cells + guard_epochs) fft_len 4: needs no handle and
+ * no device.  -1 for a NULL params, n_streams < 1, an fft_len other than 512, 1024, 2048 or 4096, epochs_per_stream < 1, cells odd or
+ * outside 2..128, guard_epochs outside 0..16, rank outside 1..cells, an alpha that is not finite or <= 0, or a nonzero reserved. */
+CRN_API int64_t crn_tcfar_hist_bytes(int64_t n_streams, int32_t fft_len, const crn_tcfar_params *params);
+
+/* Enqueue the stage on `stream`, at most three launches (device pointers):
+ *   d_spectrum  [n_epochs][fft_len]                `spectrum` rows (16-byte aligned)
+ *   d_or_mask   [n_epochs][fft_len / 32]           or NULL (8-byte aligned); may be d_bin_mask itself
+ *   d_bin_mask  [n_epochs][fft_len / 32]           or NULL (8-byte aligned)
+ *   d_rows      [n_epochs]                         or NULL (16-byte aligned)
+ *   d_hist      [n_streams][cells + guard_epochs][fft_len] float, crn_tcfar_hist_bytes of them (16-byte aligned): read (unless
+ *               first != 0), then the batch's last rows are written
+ *   d_seen      [n_streams] int64 (8-byte aligned): read (unless first != 0), then rewritten
+ * d_bin_mask and d_rows both NULL is allowed: the call then only feeds the history.  `h` supplies fft_len and the device, nothing
+ * else.  Only enqueues, allocates nothing, keeps no host state.  CRN_ERR_ARG, decided before any device call, for a NULL h, params,
+ * d_spectrum, d_hist or d_seen; n_epochs < 0; any parameter outside the ranges above; a nonzero reserved; a misaligned pointer.
+ * n_epochs = 0 succeeds, launches nothing and leaves d_hist and d_seen as they are, with first != 0 too. */
+CRN_API int crn_tcfar_device(crn_handle *h, const float *d_spectrum, int64_t n_epochs, const crn_tcfar_params *params,
+                             const uint32_t *d_or_mask, uint32_t *d_bin_mask, crn_tcfar_row *d_rows, float *d_hist, int64_t *d_seen,
+                             void *stream);
+
 /* Allocate, now, the device scratch and pinned staging that crn_sense_run_host needs for up to
  * max_epochs dense epochs of full-length frames (and their per-bin spectra when want_spectrum != 0),
  * and load the kernels: a later crn_sense_run_host within that size allocates nothing.  An engine

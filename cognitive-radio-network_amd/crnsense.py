@@ -52,6 +52,7 @@ EXPORTS = [
     "crn_fuse_device", "crn_fuse_member_pfa",
     "crn_holes_workspace_bytes", "crn_holes_device",
     "crn_lad_device", "crn_lad_factor",
+    "crn_tcfar_hist_bytes", "crn_tcfar_device",
     "crn_comm_unique_id", "crn_comm_create", "crn_comm_local", "crn_comm_allgather", "crn_comm_gathered",
     "crn_comm_finish", "crn_comm_destroy", "crn_comm_local_addr", "crn_comm_wait", "crn_comm_info",
     "crn_last_error", "crn_abi_version", "crn_build_info",
@@ -212,6 +213,21 @@ class LadParams(C.Structure):
 # numpy view of the headers crn_lad_device writes: np.frombuffer(bytes, LAD_ROW_DTYPE), one per epoch
 LAD_ROW_DTYPE = [("n_lower", "<i4"), ("n_upper", "<i4"), ("n_detected", "<i4"), ("n_clusters", "<i4"), ("n_rejected", "<i4"), ("n_clean", "<i4"),
                  ("floor_min", "<f4"), ("floor_max", "<f4")]
+
+
+class TcfarParams(C.Structure):
+    """crn_tcfar_params (crn_tcfar_device), 32 bytes."""
+    _fields_ = [("epochs_per_stream", C.c_int32), ("first", C.c_int32), ("cells", C.c_int32), ("guard_epochs", C.c_int32), ("rank", C.c_int32),
+                ("alpha", C.c_float), ("reserved", C.c_int32 * 2)]
+
+
+class TcfarRow(C.Structure):
+    """crn_tcfar_row: one epoch's header, 16 bytes."""
+    _fields_ = [("n_detected", C.c_int32), ("n_new", C.c_int32), ("n_cells", C.c_int32), ("reserved", C.c_int32)]
+
+
+# numpy view of the headers crn_tcfar_device writes: np.frombuffer(bytes, TCFAR_ROW_DTYPE), one per epoch
+TCFAR_ROW_DTYPE = [("n_detected", "<i4"), ("n_new", "<i4"), ("n_cells", "<i4"), ("reserved", "<i4")]
 CFAR_METHODS = {"ca": CFAR_CA, "go": CFAR_GO, "so": CFAR_SO, "os": CFAR_OS}
 
 
@@ -348,6 +364,9 @@ def lib():
                                        C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
         L.crn_lad_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(LadParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.crn_lad_factor.argtypes = [C.c_double, C.c_int32, C.c_double, C.POINTER(C.c_double)]
+        L.crn_tcfar_hist_bytes.argtypes, L.crn_tcfar_hist_bytes.restype = [C.c_int64, C.c_int32, C.POINTER(TcfarParams)], C.c_int64
+        L.crn_tcfar_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(TcfarParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.c_void_p, C.c_void_p]
         L.crn_ingest_create.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]
         L.crn_ingest_push.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
         L.crn_ingest_flush.argtypes = [C.c_void_p]
@@ -583,6 +602,26 @@ def lad_factor(pfa, K, t_cme=0.0):
     f = C.c_double()
     check(lib().crn_lad_factor(float(pfa), int(K), float(t_cme), C.byref(f)), "crn_lad_factor")
     return f.value
+
+
+def tcfar_params(epochs_per_stream, cells, rank, alpha, guard_epochs=1, first=False):
+    """crn_tcfar_params: alpha from tcfar_alpha(pfa, K, cells, rank)."""
+    return TcfarParams(epochs_per_stream=int(epochs_per_stream), first=int(bool(first)), cells=int(cells), guard_epochs=int(guard_epochs),
+                       rank=int(rank), alpha=float(alpha))
+
+
+def tcfar_alpha(pfa, K, cells, rank):
+    """alpha of crn_tcfar_device for a per-bin false-alarm probability pfa at K frames per epoch: the ordered-statistic CFAR's, whose
+    training cells are the bin's own `cells` earlier epochs (cfar_alpha(..., method="os") with train = cells // 2)."""
+    return cfar_alpha(pfa, K, int(cells) // 2, method="os", rank=int(rank))
+
+
+def tcfar_hist_bytes(n_streams, fft_len, params):
+    """Bytes of the history Sensor.tcfar_device carries for n_streams streams (crn_tcfar_hist_bytes): no handle, no device."""
+    nb = lib().crn_tcfar_hist_bytes(int(n_streams), int(fft_len), C.byref(params))
+    if nb <= 0:
+        raise CrnError(f"crn_tcfar_hist_bytes: arguments out of range ({nb})")
+    return nb
 
 
 def hole_hz(lo, width, fft_len, fs, fc):
@@ -907,6 +946,16 @@ class Sensor:
         v = lambda ptr: C.c_void_p(ptr or None)      # noqa: E731
         check(lib().crn_lad_device(self._h, v(spectrum_ptr), n_epochs, C.byref(params), v(or_mask_ptr), v(mask_ptr), v(rows_ptr), v(floor_ptr),
                                    v(stream)), "crn_lad_device")
+
+    def tcfar_device(self, spectrum_ptr, n_epochs, params, hist_ptr, seen_ptr, mask_ptr=0, rows_ptr=0, or_mask_ptr=0, stream=None):
+        """Ordered-statistic CFAR along time on n_epochs `spectrum` rows (device pointers; params from tcfar_params): hist_ptr
+        tcfar_hist_bytes(...) of float32 and seen_ptr [n_streams] int64, the carry, read (unless params.first) and rewritten; mask_ptr
+        [n_epochs][fft_len / 32] uint32, the CFAR mask's layout, or 0; rows_ptr [n_epochs] TCFAR_ROW_DTYPE or 0 (both 0: the call only
+        feeds the history); or_mask_ptr: a mask of the same layout OR-ed into the output (the CFAR or LAD mask of the same rows; it may be
+        mask_ptr itself), or 0.  n_streams = n_epochs / params.epochs_per_stream.  Only enqueues."""
+        v = lambda ptr: C.c_void_p(ptr or None)      # noqa: E731
+        check(lib().crn_tcfar_device(self._h, v(spectrum_ptr), n_epochs, C.byref(params), v(or_mask_ptr), v(mask_ptr), v(rows_ptr), v(hist_ptr),
+                                     v(seen_ptr), v(stream)), "crn_tcfar_device")
 
     def fuse_device(self, mask_ptr, spectrum_ptr, n_epochs, params, fused_mask_ptr=0, fused_spectrum_ptr=0, rows_ptr=0, stream=0):
         """Fuses groups of params.group_size streams (fuse_params; device pointers): mask_ptr [n_epochs][fft_len / 32] uint32 and
