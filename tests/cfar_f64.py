@@ -7,6 +7,7 @@
 import numpy as np
 
 import ref_f64
+from mask_bits import pack_mask, unpack_mask  # noqa: F401  (one definition of the mask layout; the tests take the two names from here)
 
 WINDOWS = {0: "rect", 1: "hann", 2: "bh"}
 
@@ -47,19 +48,6 @@ def decide(runs, det, min_bins):
     bb = band_bins(runs, det)
     occ = bb >= min_bins
     return bb, occ, occ.sum(axis=1)
-
-
-def pack_mask(det):
-    """[n_epochs, N] bool -> [n_epochs, N / 32] uint32, bit k % 32 of word k / 32."""
-    d = np.asarray(det, bool)
-    e, n = d.shape
-    bits = d.reshape(e, n // 32, 32).astype(np.uint64) << np.arange(32, dtype=np.uint64)
-    return bits.sum(axis=2).astype(np.uint32)
-
-
-def unpack_mask(words, n):
-    w = np.asarray(words, np.uint32).reshape(-1, n // 32)
-    return ((w[:, :, None] >> np.arange(32, dtype=np.uint32)) & 1).astype(bool).reshape(-1, n)
 
 
 def run(plan, iq, n_epochs, guard, train, alpha, min_bins, L=None, epoch_stride=0, P=None):

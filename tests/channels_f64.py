@@ -13,7 +13,7 @@ epoch after the other: the sequential rule, nothing of the kernels' chunks and j
 powers (run_sequence is the rule itself); `forecast` is crn_channel_forecast's closed form."""
 import numpy as np
 
-from segments_f64 import pack_mask, unpack_mask  # noqa: F401  (the mask layout is the segments twin's)
+from mask_bits import pack_mask, unpack_mask  # noqa: F401  (one definition of the mask layout; the tests take the two names from here)
 
 STATS = np.dtype([("n_epochs", "<i8"), ("n_busy", "<i8"), ("n_trans", "<i8", (2, 2)), ("n_runs", "<i8", (2,)), ("run_sum", "<i8", (2,)),
                   ("run_max", "<i8", (2,)), ("run", "<i8"), ("state", "<i4"), ("reserved", "<i4"), ("power", "<f8", (2,)),

@@ -12,7 +12,7 @@ of summation:
 `fuse` returns (fused det [G T][N] bool, fused row [G T][N] float32 or None, headers [G T] ROW)."""
 import numpy as np
 
-from channels_f64 import pack_mask, unpack_mask  # noqa: F401  (the mask layout is the segments twin's)
+from mask_bits import pack_mask, unpack_mask  # noqa: F401  (one definition of the mask layout; the tests take the two names from here)
 
 ROW = np.dtype([("n_detected", "<i4"), ("n_any", "<i4"), ("n_all", "<i4"), ("n_active", "<i4")])
 VOTE, SOFT = 0, 1

@@ -14,7 +14,7 @@ the holes bin after bin):
 that a comparison can bound them."""
 import numpy as np
 
-from segments_f64 import pack_mask, unpack_mask  # noqa: F401  (the tests take them from here)
+from mask_bits import pack_mask, unpack_mask  # noqa: F401  (one definition of the mask layout; the tests take the two names from here)
 
 AGE_MAX = 2 ** 31 - 1
 STREAM_F64 = np.dtype([("n_found", "<i4"), ("n_stored", "<i4"), ("free_bins", "<i4"), ("widest_lo", "<i4"), ("widest_width", "<i4"),

@@ -14,6 +14,8 @@ import math
 
 import numpy as np
 
+from mask_bits import pack_mask, unpack_mask  # noqa: F401  (one definition of the mask layout; the tests take the two names from here)
+
 ROW_DTYPE = [("n_lower", "<i4"), ("n_upper", "<i4"), ("n_detected", "<i4"), ("n_clusters", "<i4"), ("n_rejected", "<i4"), ("n_clean", "<i4"),
              ("floor_min", "<f4"), ("floor_max", "<f4")]
 ROW_INTS = ("n_lower", "n_upper", "n_detected", "n_clusters", "n_rejected", "n_clean")
@@ -112,19 +114,6 @@ def run(P, n_blocks, init_percent, t_cme, t_lower, t_upper, or_mask=None):
         mask[e] = det if or_mask is None else det | np.asarray(or_mask[e], bool)
         rows[e] = (lower.sum(), upper.sum(), mask[e].sum(), kept, rejected, clean, floors[e].min(), floors[e].max())
     return mask, rows, floors, margin
-
-
-def pack_mask(det):
-    """[E, N] bool -> [E, N / 32] uint32, bit k % 32 of word k / 32."""
-    d = np.asarray(det, bool)
-    e, n = d.shape
-    bits = d.reshape(e, n // 32, 32).astype(np.uint64) << np.arange(32, dtype=np.uint64)
-    return bits.sum(axis=2).astype(np.uint32)
-
-
-def unpack_mask(words, n):
-    w = np.asarray(words, np.uint32).reshape(-1, n // 32)
-    return ((w[:, :, None] >> np.arange(32, dtype=np.uint32)) & 1).astype(bool).reshape(-1, n)
 
 
 def compare(got_mask, got_rows, got_floors, want, what="", max_undecided=1):

@@ -10,6 +10,8 @@
 so that a comparison can round or bound them as it needs."""
 import numpy as np
 
+from mask_bits import pack_mask, unpack_mask  # noqa: F401  (one definition of the mask layout; the tests take the two names from here)
+
 EPOCH_F64 = np.dtype([("n_found", "<i4"), ("n_stored", "<i4"), ("noise_bins", "<i4"), ("noise_mean", "<f8")])
 SEGMENT_F64 = np.dtype([("lo", "<i4"), ("width", "<i4"), ("peak_bin", "<i4"), ("n_detected", "<i4"),
                         ("power", "<f8"), ("peak_power", "<f8"), ("centroid", "<f8")])
@@ -88,19 +90,6 @@ def run(det, spectrum, merge_gap=0, min_width=1, max_segments=16):
             for k, v in s.items():
                 segs[e, j][k] = v
     return eps, segs
-
-
-def pack_mask(det):
-    """[E][N] bool -> [E][N / 32] uint32, bit k % 32 of word k / 32 = bin k (the layout crn_sense_run_device_cfar writes)."""
-    det = np.asarray(det, bool)
-    E, n = det.shape
-    bits = det.reshape(E, n // 32, 32).astype(np.uint64)
-    return (bits << np.arange(32, dtype=np.uint64)).sum(axis=2).astype(np.uint32)
-
-
-def unpack_mask(words, n):
-    words = np.asarray(words).view(np.uint32).reshape(-1, n // 32)
-    return ((words[:, :, None] >> np.arange(32, dtype=np.uint32)) & 1).astype(bool).reshape(-1, n)
 
 
 REL_TOL = 2.0 ** -22     # power, centroid, noise_mean: fp64 accumulation rounded to fp32 once, against the twin's float64 value

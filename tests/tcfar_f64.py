@@ -9,6 +9,8 @@ compare every bin byte for byte.  brute() restates the rule on a whole stream wi
 The name follows the other twins'; nothing here needs float64."""
 import numpy as np
 
+from mask_bits import pack_mask, unpack_mask  # noqa: F401  (one definition of the mask layout; the tests take the two names from here)
+
 ROW_DTYPE = [("n_detected", "<i4"), ("n_new", "<i4"), ("n_cells", "<i4"), ("reserved", "<i4")]
 SEEN_MAX = 2 ** 62
 
@@ -76,15 +78,3 @@ def written_slots(seen_after, cells, guard):
     h = cells + guard
     return sorted({gl % h for gl in range(max(0, int(seen_after) - h), int(seen_after))})
 
-
-def pack_mask(det):
-    """[E, N] bool -> [E, N / 32] uint32, bit k % 32 of word k / 32."""
-    d = np.asarray(det, bool)
-    e, n = d.shape
-    bits = d.reshape(e, n // 32, 32).astype(np.uint64) << np.arange(32, dtype=np.uint64)
-    return bits.sum(axis=2).astype(np.uint32)
-
-
-def unpack_mask(words, n):
-    w = np.asarray(words, np.uint32).reshape(-1, n // 32)
-    return ((w[:, :, None] >> np.arange(32, dtype=np.uint32)) & 1).astype(bool).reshape(-1, n)

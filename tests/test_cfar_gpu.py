@@ -14,72 +14,26 @@ import signals
 pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
-DEV = "cuda"
+import stage_gpu as sgpu        # noqa: E402  (needs torch)
+from stage_gpu import DEV       # noqa: E402
+import cfar_gpu_util as cu      # noqa: E402
+
 G_, W_ = 2, 16
-# The band the comparison leaves out: |P / (alpha Z) - 1| <= DELTA_FACTOR x parity_policy.snr_bound at the traffic's in-band SNR.
-# Started at 4 x (1.57e-4 here): on the MI355X the kernel and the twin then disagreed at no bin of any case, and at most one bin of a
-# case fell inside the band.  Tightened to 2 x: the fp32 ratio carries the per-bin error of P and, at most as large, that of Z.
-DELTA_FACTOR = 2.0
 
 
-def _cfg(n, window, k, decide=cs.DECIDE_THRESHOLD):
-    c = cs.cfg_energy_scaled(n)
-    c.window = window
-    c.hop = n // 2 if window == cs.WINDOW_HANN else n
-    c.frames_per_epoch = k
-    c.decide = decide
-    return c
-
-
-def _zeros(shape, dtype):
-    return torch.zeros(shape, dtype=dtype, device=DEV)
-
-
-def _run(s, cfg, iq_t, E, L, cfar=True, spectrum=True, first=0, count=None, outs=None):
-    """One launch over epochs [first, first + count) into the (optionally given) full-size output tensors."""
-    N, nb = cfg.fft_len, cfg.n_bands
-    count = E - first if count is None else count
-    if outs is None:
-        outs = {"features": _zeros((E, nb), torch.float32), "decision": _zeros((E,), torch.int32),
-                "occupancy": _zeros((E, nb), torch.uint8), "spectrum": _zeros((E, N), torch.float32) if spectrum else None,
-                "mask": _zeros((E, N // 32), torch.int32), "band_bins": _zeros((E, nb), torch.int32)}
-    spe = cs.samples_per_epoch(cfg, L)
-    ptr = {k: (v[first].data_ptr() if v is not None else 0) for k, v in outs.items()}
-    o = {"features": ptr["features"], "ann_out": 0, "decision": ptr["decision"], "occupancy": ptr["occupancy"], "spectrum": ptr["spectrum"]}
-    iq_ptr = iq_t.data_ptr() + first * spe * 8
-    if cfar:
-        s.run_device_cfar(iq_ptr, count, L, o, mask_ptr=ptr["mask"], band_bins_ptr=ptr["band_bins"])
-    else:
-        s.run_device(iq_ptr, count, L, o)
-    return outs
-
-
-def _host(outs):
-    torch.cuda.synchronize()
-    return {k: (v.cpu().numpy() if v is not None else None) for k, v in outs.items()}
-
-
-def _snr(cfg):
-    return max(pol.in_band_snr_db(0.02, 1e-6, signals.band_bins(cfg, b).size, cfg.fft_len) for b in range(1, cfg.n_bands))
-
-
-CASES = [(n, w, k, n) for n in (512, 1024, 2048, 4096) for w in (cs.WINDOW_RECT, cs.WINDOW_HANN, cs.WINDOW_BLACKMAN_HARRIS) for k in (1, 10)]
-CASES.append((1024, cs.WINDOW_RECT, 10, 700))   # short packets: L < N, zero-padded
-
-
-@pytest.mark.parametrize("n,window,k,L", CASES)
+@pytest.mark.parametrize("n,window,k,L", cu.CASES)
 def test_mask_matches_twin(built, n, window, k, L):
-    cfg = _cfg(n, window, k)
+    cfg = cu.cfg(n, window, k)
     E = 12
     iq, _ = signals.make_epochs(cfg, E, seed=n * 31 + window * 7 + k + L, L=L)
     alpha = cs.cfar_alpha(1e-3, k, W_)
     s = cs.Sensor(cfg)
     s.set_cfar(G_, W_, alpha, 1)
-    got = _host(_run(s, cfg, torch.from_numpy(iq).to(DEV), E, L))
+    got = cu.host(cu.run(s, cfg, torch.from_numpy(iq).to(DEV), E, L))
     s.close()
     want = cf.run(cf.plan_of(cfg), iq, E, G_, W_, float(np.float32(alpha)), 1, L=L)
     det = cf.unpack_mask(got["mask"].view(np.uint32), n)
-    delta = DELTA_FACTOR * pol.snr_bound(n, _snr(cfg))
+    delta = cu.DELTA_FACTOR * pol.snr_bound(n, cu.snr(cfg))
     near = np.abs(want["ratio"] - 1) <= delta
     bad = (det != want["det"]) & ~near
     dis = np.abs(want["ratio"] - 1)[det != want["det"]]
@@ -93,21 +47,6 @@ def test_mask_matches_twin(built, n, window, k, L):
     assert (got["decision"] == dec).all()
 
 
-def _strong_tones(cfg, E, db, seed):
-    """Complex white noise (power 1e-6 per sample) plus on-grid tones `db` over the per-bin noise floor, one every N / 8 bins at
-    sixteen different offsets within a thread's 16-bin block (bins 64 + j N / 8 + 3 j)."""
-    n, k = cfg.fft_len, cfg.frames_per_epoch
-    total = E * k * (cfg.hop if cfg.hop != n else n) + (n - cfg.hop if cfg.hop != n else 0)
-    rng = np.random.default_rng(seed)
-    x = (rng.normal(0, np.sqrt(0.5e-6), total) + 1j * rng.normal(0, np.sqrt(0.5e-6), total))
-    amp = np.sqrt(10 ** (db / 10) * 1e-6 / n)          # |X|^2 = amp^2 N^2 against a floor of N 1e-6 (rect)
-    m = np.arange(total)
-    tones = [64 + j * (n // 8) + 3 * j for j in range(8)]
-    for kb in tones:
-        x += amp * np.exp(2j * np.pi * (kb * m % n) / n)
-    return x.astype(np.complex64).view(np.float32).copy(), tones
-
-
 @pytest.mark.parametrize("n,window,k", [(4096, cs.WINDOW_RECT, 10), (1024, cs.WINDOW_HANN, 10), (2048, cs.WINDOW_BLACKMAN_HARRIS, 1)])
 @pytest.mark.parametrize("db", [80, 90])
 @pytest.mark.parametrize("train", [16, 8])     # the subtraction-free sums (W >= 16) and the fp64 slide (W < 16)
@@ -116,13 +55,13 @@ def test_mask_next_to_strong_tones(built, n, window, k, db, train):
     still see the local floor.  The kernel's mask is compared with the float64 CFAR evaluated on the kernel's OWN spectrum, so that
     the fp32 transform's own error near a 90 dB carrier (~1e-2 of the floor) is not in the comparison: what is left is the CFAR pass
     (sum order and precision of the training sums, alpha / 2W rounded to fp32), held to 1e-5."""
-    cfg = _cfg(n, window, k)
+    cfg = cu.cfg(n, window, k)
     E = 6
-    iq, tones = _strong_tones(cfg, E, db, seed=db * 7 + n)
+    iq, tones = cu.strong_tones(cfg, E, db, seed=db * 7 + n)
     alpha = cs.cfar_alpha(1e-3, k, train)
     s = cs.Sensor(cfg)
     s.set_cfar(G_, train, alpha, 1)
-    got = _host(_run(s, cfg, torch.from_numpy(iq).to(DEV), E, n))
+    got = cu.host(cu.run(s, cfg, torch.from_numpy(iq).to(DEV), E, n))
     s.close()
     det = cf.unpack_mask(got["mask"].view(np.uint32), n)
     r = cf.ratio(got["spectrum"].astype(np.float64), G_, train, float(np.float32(alpha)))
@@ -138,14 +77,14 @@ def test_mask_next_to_strong_tones(built, n, window, k, db, train):
                                         (4096, cs.WINDOW_RECT, 10), (4096, cs.WINDOW_HANN, 8)])
 def test_spectrum_and_features_bit_identical_to_cfar_off(built, n, window, k):
     """CFAR on and off run the same frame loop and the same LDS band walk (a spectrum is requested: both close through LDS)."""
-    cfg = _cfg(n, window, k)
+    cfg = cu.cfg(n, window, k)
     E = 37
     iq, _ = signals.make_epochs(cfg, E, seed=5 + n)
     iq_t = torch.from_numpy(iq).to(DEV)
     s = cs.Sensor(cfg)
-    off = _host(_run(s, cfg, iq_t, E, n, cfar=False))
+    off = cu.host(cu.run(s, cfg, iq_t, E, n, cfar=False))
     s.set_cfar(G_, W_, cs.cfar_alpha(1e-3, k, W_), 1)
-    on = _host(_run(s, cfg, iq_t, E, n))
+    on = cu.host(cu.run(s, cfg, iq_t, E, n))
     s.close()
     assert off["spectrum"].tobytes() == on["spectrum"].tobytes()
     assert off["features"].tobytes() == on["features"].tobytes()
@@ -154,18 +93,18 @@ def test_spectrum_and_features_bit_identical_to_cfar_off(built, n, window, k):
 @pytest.mark.parametrize("n,window", [(1024, cs.WINDOW_RECT), (2048, cs.WINDOW_HANN), (4096, cs.WINDOW_RECT)])
 def test_cut_independence(built, n, window):
     """n_epochs not a multiple of the epochs per workgroup; one launch and four launches give the same bytes."""
-    cfg = _cfg(n, window, 10)
+    cfg = cu.cfg(n, window, 10)
     E = 37 if n < 4096 else 301
     iq, _ = signals.make_epochs(cfg, E, seed=77 + n)
     iq_t = torch.from_numpy(iq).to(DEV)
     s = cs.Sensor(cfg)
     s.set_cfar(G_, W_, cs.cfar_alpha(1e-3, 10, W_), 2)
-    whole = _host(_run(s, cfg, iq_t, E, n))
+    whole = cu.host(cu.run(s, cfg, iq_t, E, n))
     outs = None
     cuts = [0, 5, 16, 29, E]
     for a, b in zip(cuts, cuts[1:]):
-        outs = _run(s, cfg, iq_t, E, n, first=a, count=b - a, outs=outs)
-    parts = _host(outs)
+        outs = cu.run(s, cfg, iq_t, E, n, first=a, count=b - a, outs=outs)
+    parts = cu.host(outs)
     s.close()
     for key in whole:
         assert whole[key].tobytes() == parts[key].tobytes(), key
@@ -175,28 +114,16 @@ def test_false_alarm_rate_noise_only(built):
     """White complex Gaussian noise, rect, disjoint frames, N = 4096, K = 10, W = 16: the measured per-bin false-alarm rate is within
     15 % of the Pfa the alpha helper was asked for."""
     n, k, E, pfa = 4096, 10, 2400, 1e-3
-    cfg = _cfg(n, cs.WINDOW_RECT, k)
-    gen = torch.Generator(device=DEV)
-    gen.manual_seed(2024)
-    iq_t = torch.randn(E * k * n * 2, generator=gen, device=DEV, dtype=torch.float32)
+    cfg = cu.cfg(n, cs.WINDOW_RECT, k)
+    iq_t = sgpu.noise_batch(E, k, n, seed=2024)
     s = cs.Sensor(cfg)
     s.set_cfar(G_, W_, cs.cfar_alpha(pfa, k, W_), 1)
-    got = _host(_run(s, cfg, iq_t, E, n, spectrum=False))
+    got = cu.host(cu.run(s, cfg, iq_t, E, n, spectrum=False))
     s.close()
     det = cf.unpack_mask(got["mask"].view(np.uint32), n)
     rate = det.mean()
     print(f"noise only: {int(det.sum())} detections in {det.size} bin trials: false-alarm rate {rate:.4e} (asked {pfa:g})")
     assert abs(rate / pfa - 1) < 0.15, rate
-
-
-def _coloured(n, k, E, tone_bin, seed):
-    """Frames built in the frequency domain: bins [0, N/2) at power 1, [N/2, N) 10 dB above, a tone 20 dB over the low floor."""
-    rng = np.random.default_rng(seed)
-    pw = np.where(np.arange(n) < n // 2, 1.0, 10.0)
-    X = (rng.normal(size=(E * k, n)) + 1j * rng.normal(size=(E * k, n))) * np.sqrt(pw / 2)
-    X[:, tone_bin] += 10.0 * np.exp(2j * np.pi * rng.uniform(size=E * k))
-    x = np.fft.ifft(X, axis=1) * 1e-3
-    return x.astype(np.complex64).view(np.float32).reshape(-1).copy()
 
 
 def test_coloured_floor(built):
@@ -206,17 +133,17 @@ def test_coloured_floor(built):
     n, k, E, tone = 4096, 10, 16, 1000
     cfg = cs.cfg_welch(n, k, 16)           # 16 equal bands of 256 bins
     cfg.window, cfg.hop = cs.WINDOW_RECT, n
-    iq = _coloured(n, k, E, tone, 99)
+    iq = cu.coloured(n, k, E, tone, 99)
     iq_t = torch.from_numpy(iq).to(DEV)
     s = cs.Sensor(cfg)
     # calibration: the low half's band energies, x 2
-    cal = _host(_run(s, cfg, iq_t, E, n, cfar=False))
+    cal = cu.host(cu.run(s, cfg, iq_t, E, n, cfar=False))
     thr = 2.0 * float(np.median(cal["features"][:, :8]))
     s.set_thresholds([thr] * 16)
-    thr_out = _host(_run(s, cfg, iq_t, E, n, cfar=False))
+    thr_out = cu.host(cu.run(s, cfg, iq_t, E, n, cfar=False))
     assert thr_out["occupancy"][:, 8:].all(), "the threshold rule should flag the high half"
     s.set_cfar(G_, W_, cs.cfar_alpha(1e-6, k, W_), 1)
-    got = _host(_run(s, cfg, iq_t, E, n))
+    got = cu.host(cu.run(s, cfg, iq_t, E, n))
     s.close()
     det = cf.unpack_mask(got["mask"].view(np.uint32), n)
     assert det[:, tone].all(), "CFAR missed the tone"
@@ -229,23 +156,23 @@ def test_coloured_floor(built):
 
 def test_set_cfar_live_and_refusals(built):
     n = 1024
-    cfg = _cfg(n, cs.WINDOW_RECT, 10)
+    cfg = cu.cfg(n, cs.WINDOW_RECT, 10)
     E = 20
     iq, _ = signals.make_epochs(cfg, E, seed=3)
     iq_t = torch.from_numpy(iq).to(DEV)
     s = cs.Sensor(cfg)
-    base = _host(_run(s, cfg, iq_t, E, n, cfar=False))
+    base = cu.host(cu.run(s, cfg, iq_t, E, n, cfar=False))
     assert s.get_cfar() is None
     with pytest.raises(TypeError):                            # no silent "off": set_cfar(None) says it
         s.set_cfar()
     with pytest.raises(cs.CrnError, match=r"\(-4\)"):       # run_device_cfar with CFAR off
-        _run(s, cfg, iq_t, E, n)
+        cu.run(s, cfg, iq_t, E, n)
     a1, a2 = cs.cfar_alpha(1e-3, 10, W_), cs.cfar_alpha(1e-8, 10, W_)
     s.set_cfar(G_, W_, a1, 1)
-    r1 = _host(_run(s, cfg, iq_t, E, n))
+    r1 = cu.host(cu.run(s, cfg, iq_t, E, n))
     s.set_cfar(G_ + 1, W_ // 2, a2, 3)
     assert s.get_cfar() == {"guard": G_ + 1, "train": W_ // 2, "alpha": pytest.approx(a2, rel=1e-6), "min_bins": 3}
-    r2 = _host(_run(s, cfg, iq_t, E, n))
+    r2 = cu.host(cu.run(s, cfg, iq_t, E, n))
     P = r1["spectrum"].astype(np.float64)
     for r, (g, w, a) in ((r1, (G_, W_, a1)), (r2, (G_ + 1, W_ // 2, a2))):
         ratio = cf.ratio(P, g, w, float(np.float32(a)))
@@ -253,7 +180,7 @@ def test_set_cfar_live_and_refusals(built):
         assert not ((det != (ratio > 1)) & (np.abs(ratio - 1) > 1e-3)).any()
     assert r1["mask"].tobytes() != r2["mask"].tobytes()
     s.set_cfar(None)
-    back = _host(_run(s, cfg, iq_t, E, n, cfar=False))
+    back = cu.host(cu.run(s, cfg, iq_t, E, n, cfar=False))
     for key in ("features", "decision", "occupancy", "spectrum"):
         assert back[key].tobytes() == base[key].tobytes(), key
     L = cs.lib()
@@ -282,7 +209,7 @@ def test_set_cfar_live_and_refusals(built):
     a = cs.Sensor(ann)
     assert rc(a._h) == -4
     a.close()
-    none = _cfg(n, cs.WINDOW_RECT, 10, decide=cs.DECIDE_NONE)
+    none = cu.cfg(n, cs.WINDOW_RECT, 10, decide=cs.DECIDE_NONE)
     s2 = cs.Sensor(none)
     assert rc(s2._h) == 0
     s2.close()
@@ -296,11 +223,11 @@ def test_sc16_refused(built):
     L.crn_sense_run_device_sc16.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.POINTER(cs.Out), C.c_void_p]
     L.crn_sense_destroy.argtypes = [C.c_void_p]
     h = C.c_void_p()
-    assert L.crn_sense_create(C.byref(_cfg(1024, cs.WINDOW_RECT, 10)), C.byref(h)) == 0
+    assert L.crn_sense_create(C.byref(cu.cfg(1024, cs.WINDOW_RECT, 10)), C.byref(h)) == 0
     q = cs.CfarParams(guard=2, train=16, min_bins=1, reserved=0, alpha=10.0)
     assert L.crn_sense_set_cfar(h, C.byref(q)) == 0
-    buf = _zeros((1024 * 10 * 2,), torch.int16)
-    dec = _zeros((1,), torch.int32)
+    buf = sgpu.zeros((1024 * 10 * 2,), torch.int16)
+    dec = sgpu.zeros((1,), torch.int32)
     o = cs.Out(features=None, ann_out=None, decision=dec.data_ptr(), occupancy=None, spectrum=None)
     assert L.crn_sense_run_device_sc16(h, buf.data_ptr(), 1, 1024, 0, C.byref(o), None) == cs.CRN_ERR_ARG
     assert L.crn_sense_destroy(h) == 0
@@ -312,37 +239,23 @@ SPEED_RATIO = 1.15
 
 def test_speed_relative_to_cfar_off(built):
     """N = 4096, K = 10, rect, 64 equal bands, >= 2 GiB per launch: device-event time of the CFAR handle against the same
-    configuration with CFAR off.  Each timed window holds R launches issued back to back behind one launch already queued, so the
-    device never waits for the host inside it; the two handles alternate, 5 windows each after a warm-up, the best window counts."""
+    configuration with CFAR off, by the method of tests/stage_gpu.py (best_of_windows): each timed window holds 8 launches issued back
+    to back behind one launch already queued, so the device never waits for the host inside it; the two handles alternate, 5 windows
+    each after a warm-up, the best window counts."""
     n, k = 4096, 10
     cfg = cs.cfg_welch(n, k, 64)
     cfg.window, cfg.hop = cs.WINDOW_RECT, n
     E = 6656                                  # 6656 x 10 x 4096 x 8 B = 2.18 GB
-    gen = torch.Generator(device=DEV)
-    gen.manual_seed(5)
-    iq_t = torch.randn(E * k * n * 2, generator=gen, device=DEV, dtype=torch.float32)
+    iq_t = sgpu.noise_batch(E, k, n)
     off, on = cs.Sensor(cfg), cs.Sensor(cfg)
     on.set_cfar(G_, W_, cs.cfar_alpha(1e-3, k, W_), 1)
-    o_off = _run(off, cfg, iq_t, E, n, cfar=False, spectrum=False)
-    o_on = _run(on, cfg, iq_t, E, n, spectrum=False)
+    o_off = cu.run(off, cfg, iq_t, E, n, cfar=False, spectrum=False)
+    o_on = cu.run(on, cfg, iq_t, E, n, spectrum=False)
     torch.cuda.synchronize()
-
-    R = 8
-
-    def timed(fn):
-        """ms per launch over R launches; the launch before the start event keeps the device busy while the host issues the rest"""
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        fn()
-        a.record()
-        for _ in range(R):
-            fn()
-        b.record()
-        b.synchronize()
-        return a.elapsed_time(b) / R
-    t_off, t_on = [], []
-    for _ in range(5):
-        t_off.append(timed(lambda: _run(off, cfg, iq_t, E, n, cfar=False, spectrum=False, outs=o_off)))
-        t_on.append(timed(lambda: _run(on, cfg, iq_t, E, n, spectrum=False, outs=o_on)))
+    # the two first launches above were the warm-up
+    times = sgpu.best_of_windows({"off": lambda: cu.run(off, cfg, iq_t, E, n, cfar=False, spectrum=False, outs=o_off),
+                                  "on": lambda: cu.run(on, cfg, iq_t, E, n, spectrum=False, outs=o_on)}, warm_up=False, report=False)
+    t_off, t_on = times["off"], times["on"]
     off.close()
     on.close()
     nbytes = E * k * n * 8

@@ -12,12 +12,14 @@ import cfar_methods_f64 as cm
 import crnsense as cs
 import parity_policy as pol
 import signals
-import test_cfar_gpu as base
 
 pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
-DEV = "cuda"
+import stage_gpu as sgpu        # noqa: E402  (needs torch)
+from stage_gpu import DEV       # noqa: E402
+import cfar_gpu_util as base    # noqa: E402
+
 G_, W_ = 2, 16
 OS_RANK = 24
 METHODS = [("go", 0), ("so", 0), ("os", OS_RANK)]
@@ -31,19 +33,19 @@ def _set(s, method, rank, pfa=1e-3, train=W_, guard=G_, min_bins=1):
 
 @pytest.mark.parametrize("n,window,k,L", base.CASES)
 def test_mask_matches_twin(built, n, window, k, L):
-    """Every method against the float64 twin outside the tolerance band of test_cfar_gpu.py; the per-band results are what the
+    """Every method against the float64 twin outside the tolerance band of cfar_gpu_util.py; the per-band results are what the
     kernel's own mask implies; OS at K = 1 (where `spectrum` is the K-frame sum itself) equals the fp32 counting twin at every bin."""
-    cfg = base._cfg(n, window, k)
+    cfg = base.cfg(n, window, k)
     E = 12
     iq, _ = signals.make_epochs(cfg, E, seed=n * 31 + window * 7 + k + L + 1, L=L)
     iq_t = torch.from_numpy(iq).to(DEV)
     plan = cf.plan_of(cfg)
     P = None
-    delta = base.DELTA_FACTOR * pol.snr_bound(n, base._snr(cfg))
+    delta = base.DELTA_FACTOR * pol.snr_bound(n, base.snr(cfg))
     s = cs.Sensor(cfg)
     for method, rank in METHODS:
         a32 = _set(s, method, rank)
-        got = base._host(base._run(s, cfg, iq_t, E, L))
+        got = base.host(base.run(s, cfg, iq_t, E, L))
         want = cm.run(plan, iq, E, G_, W_, a32, 1, method, rank, L=L, P=P)
         P = want["spectrum"]
         det = cf.unpack_mask(got["mask"].view(np.uint32), n)
@@ -65,13 +67,13 @@ def test_mask_matches_twin(built, n, window, k, L):
 def test_os_exact_next_to_strong_tones(built, n, window, k, train):
     """Tones 90 dB over the floor: OS against the counting rule evaluated in fp32 on the kernel's own K-frame sums, exactly at K = 1
     (spectrum = the sum) and outside 1e-6 of the threshold otherwise (spectrum = sum / K)."""
-    cfg = base._cfg(n, window, k)
+    cfg = base.cfg(n, window, k)
     E = 6
-    iq, tones = base._strong_tones(cfg, E, 90, seed=n + train)
+    iq, tones = base.strong_tones(cfg, E, 90, seed=n + train)
     rank = 3 * 2 * train // 4
     s = cs.Sensor(cfg)
     a32 = _set(s, "os", rank, train=train)
-    got = base._host(base._run(s, cfg, torch.from_numpy(iq).to(DEV), E, n))
+    got = base.host(base.run(s, cfg, torch.from_numpy(iq).to(DEV), E, n))
     s.close()
     det = cf.unpack_mask(got["mask"].view(np.uint32), n)
     if k == 1:
@@ -87,23 +89,23 @@ def test_os_exact_next_to_strong_tones(built, n, window, k, train):
                                         (4096, cs.WINDOW_RECT, 10), (4096, cs.WINDOW_HANN, 8)])
 def test_bit_identity(built, n, window, k):
     """set_cfar_ex(CA) gives the bytes set_cfar gives; spectrum and features are the bytes of CFAR off for every method."""
-    cfg = base._cfg(n, window, k)
+    cfg = base.cfg(n, window, k)
     E = 37
     iq, _ = signals.make_epochs(cfg, E, seed=9 + n)
     iq_t = torch.from_numpy(iq).to(DEV)
     s = cs.Sensor(cfg)
-    off = base._host(base._run(s, cfg, iq_t, E, n, cfar=False))
+    off = base.host(base.run(s, cfg, iq_t, E, n, cfar=False))
     a = cs.cfar_alpha(1e-3, k, W_)
     s.set_cfar(G_, W_, a, 2)
-    ca = base._host(base._run(s, cfg, iq_t, E, n))
+    ca = base.host(base.run(s, cfg, iq_t, E, n))
     q = cs.CfarParamsEx(method=cs.CFAR_CA, guard=G_, train=W_, min_bins=2, rank=0, reserved=0, alpha=a)
     assert cs.lib().crn_sense_set_cfar_ex(s._h, C.byref(q)) == 0
-    ca_ex = base._host(base._run(s, cfg, iq_t, E, n))
+    ca_ex = base.host(base.run(s, cfg, iq_t, E, n))
     for key in ca:
         assert ca[key].tobytes() == ca_ex[key].tobytes(), key
     for method, rank in METHODS:
         _set(s, method, rank)
-        on = base._host(base._run(s, cfg, iq_t, E, n))
+        on = base.host(base.run(s, cfg, iq_t, E, n))
         assert off["spectrum"].tobytes() == on["spectrum"].tobytes(), method
         assert off["features"].tobytes() == on["features"].tobytes(), method
     s.close()
@@ -111,18 +113,18 @@ def test_bit_identity(built, n, window, k):
 
 @pytest.mark.parametrize("n,window", [(1024, cs.WINDOW_RECT), (4096, cs.WINDOW_RECT)])
 def test_os_cut_independence(built, n, window):
-    cfg = base._cfg(n, window, 10)
+    cfg = base.cfg(n, window, 10)
     E = 37 if n < 4096 else 301
     iq, _ = signals.make_epochs(cfg, E, seed=78 + n)
     iq_t = torch.from_numpy(iq).to(DEV)
     s = cs.Sensor(cfg)
     _set(s, "os", OS_RANK, min_bins=2)
-    whole = base._host(base._run(s, cfg, iq_t, E, n))
+    whole = base.host(base.run(s, cfg, iq_t, E, n))
     outs = None
     cuts = [0, 5, 16, 29, E]
     for a, b in zip(cuts, cuts[1:]):
-        outs = base._run(s, cfg, iq_t, E, n, first=a, count=b - a, outs=outs)
-    parts = base._host(outs)
+        outs = base.run(s, cfg, iq_t, E, n, first=a, count=b - a, outs=outs)
+    parts = base.host(outs)
     s.close()
     for key in whole:
         assert whole[key].tobytes() == parts[key].tobytes(), key
@@ -132,15 +134,13 @@ def test_false_alarm_rate_noise_only(built):
     """White complex Gaussian noise, rect, disjoint frames, N = 4096, K = 10, W = 16, 2400 epochs, asked 1e-3: the measured per-bin
     rate is within 15 % for GO, SO and OS (rank 24)."""
     n, k, E, pfa = 4096, 10, 2400, 1e-3
-    cfg = base._cfg(n, cs.WINDOW_RECT, k)
-    gen = torch.Generator(device=DEV)
-    gen.manual_seed(2025)
-    iq_t = torch.randn(E * k * n * 2, generator=gen, device=DEV, dtype=torch.float32)
+    cfg = base.cfg(n, cs.WINDOW_RECT, k)
+    iq_t = sgpu.noise_batch(E, k, n, seed=2025)
     s = cs.Sensor(cfg)
     rates = {}
     for method, rank in METHODS:
         _set(s, method, rank, pfa)
-        got = base._host(base._run(s, cfg, iq_t, E, n, spectrum=False))
+        got = base.host(base.run(s, cfg, iq_t, E, n, spectrum=False))
         det = cf.unpack_mask(got["mask"].view(np.uint32), n)
         rates[method] = det.mean()
         print(f"noise only, {method}: {int(det.sum())} detections in {det.size} bin trials: {rates[method]:.4e} (asked {pfa:g})")
@@ -163,13 +163,13 @@ def test_masking(built):
     """g = 2, W = 16, Pfa 1e-6: the +45 dB carrier sits in the weak tone's training window.  OS (rank 24) detects both tones in every
     epoch; CA misses the weak one in at least 90 % of them (the scenario is real)."""
     n, k, E = 4096, 10, 40
-    cfg = base._cfg(n, cs.WINDOW_RECT, k)
+    cfg = base.cfg(n, cs.WINDOW_RECT, k)
     iq_t = torch.from_numpy(_two_tones(n, k, E, 31)).to(DEV)
     s = cs.Sensor(cfg)
     _set(s, "os", OS_RANK, 1e-6)
-    d_os = cf.unpack_mask(base._host(base._run(s, cfg, iq_t, E, n))["mask"].view(np.uint32), n)
+    d_os = cf.unpack_mask(base.host(base.run(s, cfg, iq_t, E, n))["mask"].view(np.uint32), n)
     _set(s, "ca", 0, 1e-6)
-    d_ca = cf.unpack_mask(base._host(base._run(s, cfg, iq_t, E, n))["mask"].view(np.uint32), n)
+    d_ca = cf.unpack_mask(base.host(base.run(s, cfg, iq_t, E, n))["mask"].view(np.uint32), n)
     s.close()
     print(f"masking: OS strong {d_os[:, 1000].mean():.2f} weak {d_os[:, 1008].mean():.2f}; CA strong {d_ca[:, 1000].mean():.2f} "
           f"weak {d_ca[:, 1008].mean():.2f}")
@@ -178,17 +178,17 @@ def test_masking(built):
 
 
 def test_clutter_edge(built):
-    """The 10 dB step of test_cfar_gpu._coloured, 400 epochs, Pfa 1e-3: in the g + W bins on the high side of both edges (N/2 and the
+    """The 10 dB step of cfar_gpu_util.coloured, 400 epochs, Pfa 1e-3: in the g + W bins on the high side of both edges (N/2 and the
     wrap) GO's false-alarm rate is <= 1e-2 (model 3.6e-3) and CA's >= 3e-2 (model 6.6e-2)."""
     n, k, E = 4096, 10, 400
-    cfg = base._cfg(n, cs.WINDOW_RECT, k)
-    iq_t = torch.from_numpy(base._coloured(n, k, E, 1000, 404)).to(DEV)
+    cfg = base.cfg(n, cs.WINDOW_RECT, k)
+    iq_t = torch.from_numpy(base.coloured(n, k, E, 1000, 404)).to(DEV)
     hi = np.r_[n // 2:n // 2 + G_ + W_, n - G_ - W_:n]
     s = cs.Sensor(cfg)
     rate = {}
     for method in ("go", "ca"):
         _set(s, method, 0)
-        det = cf.unpack_mask(base._host(base._run(s, cfg, iq_t, E, n, spectrum=False))["mask"].view(np.uint32), n)
+        det = cf.unpack_mask(base.host(base.run(s, cfg, iq_t, E, n, spectrum=False))["mask"].view(np.uint32), n)
         rate[method] = det[:, hi].mean()
         assert det[:, 1000].all(), method
     s.close()
@@ -198,7 +198,7 @@ def test_clutter_edge(built):
 
 def test_set_cfar_ex_live_and_refusals(built):
     n = 1024
-    cfg = base._cfg(n, cs.WINDOW_RECT, 10)
+    cfg = base.cfg(n, cs.WINDOW_RECT, 10)
     E = 20
     iq, _ = signals.make_epochs(cfg, E, seed=4)
     iq_t = torch.from_numpy(iq).to(DEV)
@@ -212,7 +212,7 @@ def test_set_cfar_ex_live_and_refusals(built):
         if method != "ca":
             want.update(method=method, rank=rank)
         assert s.get_cfar() == want
-        r = base._host(base._run(s, cfg, iq_t, E, n))
+        r = base.host(base.run(s, cfg, iq_t, E, n))
         ratio = cm.ratio(r["spectrum"].astype(np.float64), G_, W_, a32, method, rank)
         det = cf.unpack_mask(r["mask"].view(np.uint32), n)
         assert not ((det != (ratio > 1)) & (np.abs(ratio - 1) > 1e-3)).any(), method
@@ -235,7 +235,7 @@ def test_set_cfar_ex_live_and_refusals(built):
                 {"a": float("nan")}, {"m": 0}, {"g": 500, "w": 12}):
         assert rc(s._h, **bad) == cs.CRN_ERR_ARG, bad
     assert s.get_cfar() == before
-    r = base._host(base._run(s, cfg, iq_t, E, n))
+    r = base.host(base.run(s, cfg, iq_t, E, n))
     ratio = cm.ratio(r["spectrum"].astype(np.float64), G_, 8, before["alpha"], "os", 5)
     det = cf.unpack_mask(r["mask"].view(np.uint32), n)
     assert not ((det != (ratio > 1)) & (np.abs(ratio - 1) > 1e-3)).any()
@@ -268,15 +268,14 @@ SPEED = {"go": 1.15, "so": 1.15, "os": 1.40}
 
 def test_speed_relative_to_cfar_off(built):
     """The method and shape of test_cfar_gpu.test_speed_relative_to_cfar_off, one method at a time: N = 4096, K = 10, rect, 64 bands,
-    2.18 GB per launch, R launches back to back behind one already queued, the method's handle and the CFAR-off handle alternating,
-    5 windows each, the best counts.  CA and OS at W = 64 are printed for the record."""
+    2.18 GB per launch, 8 launches back to back behind one already queued, the method's handle and the CFAR-off handle alternating,
+    5 windows each, the best counts (tests/stage_gpu.py, best_of_windows, without its extra warm-up call).  CA and OS at W = 64 are
+    printed for the record."""
     n, k = 4096, 10
     cfg = cs.cfg_welch(n, k, 64)
     cfg.window, cfg.hop = cs.WINDOW_RECT, n
     E = 6656
-    gen = torch.Generator(device=DEV)
-    gen.manual_seed(5)
-    iq_t = torch.randn(E * k * n * 2, generator=gen, device=DEV, dtype=torch.float32)
+    iq_t = sgpu.noise_batch(E, k, n)
     forms = {"off": None, "ca": ("ca", 0, W_), "go": ("go", 0, W_), "so": ("so", 0, W_), "os": ("os", OS_RANK, W_),
              "os64": ("os", 96, 64)}
     handles, outs = {}, {}
@@ -285,30 +284,16 @@ def test_speed_relative_to_cfar_off(built):
         if f is not None:
             _set(s, f[0], f[1], train=f[2])
         handles[name] = s
-        outs[name] = base._run(s, cfg, iq_t, E, n, cfar=f is not None, spectrum=False)
+        outs[name] = base.run(s, cfg, iq_t, E, n, cfar=f is not None, spectrum=False)
     torch.cuda.synchronize()
-    R = 8
 
-    def timed(name):
-        s, o, on = handles[name], outs[name], forms[name] is not None
-
-        def fn():
-            base._run(s, cfg, iq_t, E, n, cfar=on, spectrum=False, outs=o)
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        fn()
-        a.record()
-        for _ in range(R):
-            fn()
-        b.record()
-        b.synchronize()
-        return a.elapsed_time(b) / R
+    def launch(name):
+        return lambda: base.run(handles[name], cfg, iq_t, E, n, cfar=forms[name] is not None, spectrum=False, outs=outs[name])
     nbytes = E * k * n * 8
     ratio = {}
     for name in ("ca", "go", "so", "os", "os64"):
-        t_off, t_on = [], []
-        for _ in range(5):
-            t_off.append(timed("off"))
-            t_on.append(timed(name))
+        times = sgpu.best_of_windows({"off": launch("off"), name: launch(name)}, warm_up=False, report=False)
+        t_off, t_on = times["off"], times[name]
         b_off, b_on = min(t_off), min(t_on)
         ratio[name] = b_on / b_off
         gbs = nbytes / (b_on * 1e-3) / 1e9

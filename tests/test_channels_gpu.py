@@ -16,61 +16,30 @@ import crnsense as cs
 pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
-DEV = "cuda"
+import stage_gpu as sgpu        # noqa: E402  (needs torch)
+from stage_gpu import DEV       # noqa: E402
+
 G_, W_ = 2, 16
 SIZES = (512, 1024, 2048, 4096)
-PAD = 256                      # bytes of 0xFF kept behind every output array
-
-
-def _cfg(n, window, k, bands=None):
-    c = cs.cfg_energy_scaled(n) if bands is None else cs.cfg_welch(n, k, bands)
-    c.window = window
-    c.hop = n // 2 if window == cs.WINDOW_HANN else n
-    c.frames_per_epoch = k
-    return c
-
-
-def _zeros(shape, dtype):
-    return torch.zeros(shape, dtype=dtype, device=DEV)
-
-
-def _cfar(s, cfg, iq_t, E, outs=None):
-    """One CFAR launch over E epochs with `spectrum`, the mask and band_bins written; returns the device tensors."""
-    N, nb = cfg.fft_len, cfg.n_bands
-    if outs is None:
-        outs = {"features": _zeros((E, nb), torch.float32), "decision": _zeros((E,), torch.int32), "occupancy": _zeros((E, nb), torch.uint8),
-                "spectrum": _zeros((E, N), torch.float32), "mask": _zeros((E, N // 32), torch.int32), "band_bins": _zeros((E, nb), torch.int32)}
-    o = {"features": outs["features"].data_ptr(), "ann_out": 0, "decision": outs["decision"].data_ptr(),
-         "occupancy": outs["occupancy"].data_ptr(), "spectrum": outs["spectrum"].data_ptr()}
-    s.run_device_cfar(iq_t.data_ptr(), E, N, o, mask_ptr=outs["mask"].data_ptr(), band_bins_ptr=outs["band_bins"].data_ptr())
-    return outs
 
 
 def _spans(spans):
     return [(sp.lo, sp.width) if isinstance(sp, cs.ChannelSpan) else tuple(sp) for sp in spans]
 
 
-class _Out:
-    """The records, d_busy and d_power of a batch on the device, each with PAD bytes behind it, all filled with 0xFF first so that
-    whatever the kernels skipped, or wrote past the end, shows.  The workspace is exactly the size the library asks for."""
+class _Out(sgpu.Padded):
+    """The records, d_busy and d_power of a batch on the device, each with 0xFF bytes behind it (stage_gpu.Padded).  The workspace is
+    exactly the size the library asks for."""
 
     def __init__(self, E, n_streams, nch, spans, eps, min_bins=1):
         self.E, self.S, self.C = E, n_streams, nch
-        self.stats = torch.full((n_streams * nch * 192 + PAD,), 255, dtype=torch.uint8, device=DEV)
-        self.busy = torch.full((E * 8 + PAD,), 255, dtype=torch.uint8, device=DEV)
-        self.power = torch.full((E * nch * 4 + PAD,), 255, dtype=torch.uint8, device=DEV)
+        super().__init__(stats=n_streams * nch * 192, busy=E * 8, power=E * nch * 4)
         self.ws_bytes = cs.channels_workspace_bytes(E, spans, eps, min_bins)
         self.ws = torch.full((self.ws_bytes,), 255, dtype=torch.uint8, device=DEV)
 
     def host(self):
-        torch.cuda.synchronize()
-        st, bu, pw = self.stats.cpu().numpy(), self.busy.cpu().numpy(), self.power.cpu().numpy()
-        self.pads = (st[self.S * self.C * 192:], bu[self.E * 8:], pw[self.E * self.C * 4:])
-        return (np.frombuffer(st[: self.S * self.C * 192].tobytes(), cs.CHANNEL_STATS_DTYPE).reshape(self.S, self.C),
-                np.frombuffer(bu[: self.E * 8].tobytes(), np.uint64), np.frombuffer(pw[: self.E * self.C * 4].tobytes(), np.float32).reshape(self.E, self.C))
-
-    def pads_untouched(self):
-        return all((p == 255).all() for p in self.pads)
+        super().host()
+        return self.view("stats", cs.CHANNEL_STATS_DTYPE, (self.S, self.C)), self.view("busy", np.uint64), self.view("power", np.float32, (self.E, self.C))
 
 
 def _run(s, mask_t, spec_t, E, spans, eps, min_bins=1, first=True, out=None, busy=True, power=True):
@@ -83,7 +52,7 @@ def _run(s, mask_t, spec_t, E, spans, eps, min_bins=1, first=True, out=None, bus
 
 
 def _upload(det, P):
-    return (torch.from_numpy(ch.pack_mask(det).view(np.int32)).to(DEV), None if P is None else torch.from_numpy(np.ascontiguousarray(P, np.float32)).to(DEV))
+    return sgpu.upload_mask(det), None if P is None else sgpu.upload_rows(P)
 
 
 def _check(s, det, P, spans, eps, min_bins, what):
@@ -127,7 +96,7 @@ def test_spans_against_twin(built, n):
     E = 6
     det = rng.random((E, n)) < np.array([0.0, 0.002, 0.05, 0.5, 0.95, 1.0])[:, None]
     P = (rng.gamma(10.0, 1e-4, (E, n)) * np.where(rng.random((E, n)) < 0.02, 1e4, 1.0)).astype(np.float32)
-    s = cs.Sensor(_cfg(n, cs.WINDOW_RECT, 10))
+    s = cs.Sensor(sgpu.cfg(n, cs.WINDOW_RECT, 10))
     worst = 0.0
     for nch, spans in span_sets(n, rng).items():
         assert len(spans) == nch
@@ -173,7 +142,7 @@ def test_time_sequences_against_twin(built, eps, n_streams):
                               _chain(rng, eps, (0.02, 0.5, 0.98, 0.02)[kind - 4], c & 1 if kind != 7 else 1 - (c >> 3 & 1)))
     det, spans = _det_from_bits(bits.reshape(E, nch), n, nch)
     P = rng.gamma(10.0, 1e-4, (E, n)).astype(np.float32)
-    s = cs.Sensor(_cfg(n, cs.WINDOW_RECT, 10))
+    s = cs.Sensor(sgpu.cfg(n, cs.WINDOW_RECT, 10))
     st, worst = _check(s, det, P, spans, eps, 1, f"eps {eps} x {n_streams} streams")
     s.close()
     assert (st["n_busy"] == bits.sum(axis=1)).all()
@@ -191,7 +160,7 @@ def test_one_flip_at_every_position(built):
             pos = 64 * st + c + 1
             bits[st, :, c] = ((t >= pos) if c % 2 == 0 else (t < pos)) if pos < eps else c % 2
     det, spans = _det_from_bits(bits.reshape(-1, nch), n, nch)
-    s = cs.Sensor(_cfg(n, cs.WINDOW_RECT, 10))
+    s = cs.Sensor(sgpu.cfg(n, cs.WINDOW_RECT, 10))
     got, _ = _check(s, det, None, spans, eps, 1, "one flip")
     s.close()
     for st in range(n_streams):
@@ -218,7 +187,7 @@ def test_strong_neighbour(built, n):
         P[:, (lo + w) % n] = 1e-3 * 1e9 * rng.uniform(0.5, 2.0, E)
     spans = inner + [(0, n), (3 * B - 1, B + 2)]
     det = rng.random((E, n)) < 0.05
-    s = cs.Sensor(_cfg(n, cs.WINDOW_RECT, 10))
+    s = cs.Sensor(sgpu.cfg(n, cs.WINDOW_RECT, 10))
     _, worst = _check(s, det, P.astype(np.float32), spans, E, 1, f"strong neighbour N={n}")
     s.close()
     ratio = P.astype(np.float32)[:, [(lo - 1) % n for lo, _ in inner]].min() / P[:, 3 * B: 4 * B].sum(axis=1).max()
@@ -239,7 +208,7 @@ def test_cut_independence(built, n, n_streams):
     det, spans = _det_from_bits(bits.reshape(-1, nch), n, nch)
     det |= rng.random(det.shape) < 0.01
     P = rng.gamma(10.0, 1e-4, det.shape).astype(np.float32)
-    s = cs.Sensor(_cfg(n, cs.WINDOW_RECT, 10))
+    s = cs.Sensor(sgpu.cfg(n, cs.WINDOW_RECT, 10))
     mask_t, spec_t = _upload(det, P)
     whole = _run(s, mask_t, spec_t, n_streams * T, spans, T, 2)
     w_st, w_busy, w_power = whole.host()
@@ -290,7 +259,7 @@ def test_agreement_with_the_fused_kernel(built, n):
     iq, _ = signals.make_epochs(cfg, E, seed=n + 64)
     s = cs.Sensor(cfg)
     s.set_cfar(G_, W_, cs.cfar_alpha(1e-2, k, W_), mb)
-    outs = _cfar(s, cfg, torch.from_numpy(iq).to(DEV), E)
+    outs = sgpu.cfar_launch(s, cfg, torch.from_numpy(iq).to(DEV), E)
     spans = cs.channel_spans_from_bands(cfg)
     out = _run(s, outs["mask"], outs["spectrum"], E, spans, E, mb)
     st, busy, power = out.host()
@@ -320,8 +289,8 @@ def test_end_to_end_markov_chain(built):
     them lie within 4 binomial standard deviations, sqrt(p (1 - p) / n) with n the observed transitions out of busy, of 0.1, 0.5, 0.6."""
     n, k, S, T = E2E["n"], E2E["k"], E2E["n_streams"], E2E["eps"]
     E = S * T
-    cfg = _cfg(n, cs.WINDOW_RECT, k)
-    iq_t = _zeros((cs.samples_needed(cfg, E) * 2,), torch.float32)
+    cfg = sgpu.cfg(n, cs.WINDOW_RECT, k)
+    iq_t = sgpu.zeros((cs.samples_needed(cfg, E) * 2,), torch.float32)
     truth_t = torch.full((E,), -1, dtype=torch.int32, device=DEV)
     sc = cs.SynthCfg()
     sc.seed, sc.noise_power, sc.signal_rms = E2E["seed"], E2E["noise_power"], E2E["signal_rms"]
@@ -329,7 +298,7 @@ def test_end_to_end_markov_chain(built):
     s = cs.Sensor(cfg)
     s.synth_fill_device_ex(iq_t.data_ptr(), E, cs.samples_per_epoch(cfg), sc, truth_ptr=truth_t.data_ptr())
     s.set_cfar(G_, W_, cs.cfar_alpha(E2E["pfa"], k, W_), 1)
-    outs = _cfar(s, cfg, iq_t, E)
+    outs = sgpu.cfar_launch(s, cfg, iq_t, E)
     out = _run(s, outs["mask"], outs["spectrum"], E, E2E["spans"], T, E2E["min_bins"])
     st, busy, power = out.host()
     truth = truth_t.cpu().numpy()
@@ -402,45 +371,25 @@ SPEED_RATIO = 1.158
 
 
 def test_cost_next_to_the_cfar_launch(built):
-    """N = 4096, K = 10, rect, 64 bands, the 2.18 GB batch; the method of tests/test_segments_gpu.py's cost test: each timed window holds
-    R launches issued back to back behind one already queued, the arms alternate, 5 windows each after a warm-up, the best counts.  Arm A
+    """N = 4096, K = 10, rect, 64 bands, the 2.18 GB batch; the method of tests/stage_gpu.py (best_of_windows): each timed window holds
+    8 launches issued back to back behind one already queued, the arms alternate, 5 windows each after a warm-up, the best counts.  Arm A
     is the CFAR launch alone, arm B the same launch followed by crn_channels_device on the same stream: 64 channels (the plan's bands),
     one stream of 6656 epochs, the hardest case for the time stage, d_busy and d_power NULL.  64 streams of 104 epochs, and the stage
     alone in both layouts, are measured the same way and printed."""
     n, k = 4096, 10
-    cfg = _cfg(n, cs.WINDOW_RECT, k, bands=64)
+    cfg = sgpu.cfg(n, cs.WINDOW_RECT, k, bands=64)
     E = 6656                                  # 6656 x 10 x 4096 x 8 B = 2.18 GB
-    gen = torch.Generator(device=DEV)
-    gen.manual_seed(5)
-    iq_t = torch.randn(E * k * n * 2, generator=gen, device=DEV, dtype=torch.float32)
-    # the traffic of the segments cost test: tones over unit noise in two epochs of three, so that channels go busy and idle
-    t = torch.arange(n, device=DEV, dtype=torch.float32)
-    frames = iq_t.view(E, k, n, 2)
-    for j, b in enumerate((300, 301, 302, 303, 1600, 1601, 1602, 3000)):
-        ph = 2 * np.pi * ((b * t) % n) / n
-        sel = slice(j % 3, E, 3)
-        frames[sel, :, :, 0] += 0.3 * torch.cos(ph)
-        frames[sel, :, :, 1] += 0.3 * torch.sin(ph)
+    # the traffic of every cost test here: tones over unit noise in two epochs of three, so that channels go busy and idle
+    iq_t = sgpu.add_tones(sgpu.noise_batch(E, k, n), E, k, n)
     s = cs.Sensor(cfg)
     s.set_cfar(G_, W_, cs.cfar_alpha(1e-3, k, W_), 1)
-    outs = _cfar(s, cfg, iq_t, E)
+    outs = sgpu.cfar_launch(s, cfg, iq_t, E)
     spans = _spans(cs.channel_spans_from_bands(cfg))
     one, many = _Out(E, 1, 64, spans, E), _Out(E, 64, 64, spans, 104)
     torch.cuda.synchronize()
-    R = 8
-
-    def timed(fn):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        fn()
-        a.record()
-        for _ in range(R):
-            fn()
-        b.record()
-        b.synchronize()
-        return a.elapsed_time(b) / R
 
     def arm_a():
-        _cfar(s, cfg, iq_t, E, outs=outs)
+        sgpu.cfar_launch(s, cfg, iq_t, E, outs=outs)
 
     def stage(out, eps):
         _run(s, outs["mask"], outs["spectrum"], E, spans, eps, 1, first=True, out=out, busy=False, power=False)
@@ -450,18 +399,10 @@ def test_cost_next_to_the_cfar_launch(built):
         stage(out, eps)
     arms = {"A": arm_a, "B one stream": arm_b, "B 64 streams": lambda: arm_b(many, 104), "alone one stream": lambda: stage(one, E),
             "alone 64 streams": lambda: stage(many, 104)}
-    for fn in arms.values():
-        fn()
-    torch.cuda.synchronize()
-    times = {name: [] for name in arms}
-    for _ in range(5):
-        for name, fn in arms.items():
-            times[name].append(timed(fn))
+    times = sgpu.best_of_windows(arms)
     st_one, st_many = one.host()[0], many.host()[0]
     s.close()
     best = {name: min(v) for name, v in times.items()}
-    for name, v in times.items():
-        print(f"ms per launch, {name}:", " ".join(f"{x:.4f}" for x in v))
     nbytes = E * k * n * 8
     moved = E * (n * 4 + n // 8 + 2 * (8 + 64 * 4))
     print(f"N=4096 K=10 rect 64 bands, {E} epochs ({nbytes / 1e9:.2f} GB), spectrum written: arm A (CFAR launch alone) {best['A']:.4f} ms "

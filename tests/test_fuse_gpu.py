@@ -14,63 +14,30 @@ import fuse_f64 as fu
 pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
-DEV = "cuda"
+import stage_gpu as sgpu        # noqa: E402  (needs torch)
+from stage_gpu import DEV       # noqa: E402
+
 G_, W_ = 2, 16
 SIZES = (512, 1024, 2048, 4096)
-PAD = 256                      # bytes of 0xFF kept behind every output array
 
 
-def _cfg(n, window, k, bands=None):
-    c = cs.cfg_energy_scaled(n) if bands is None else cs.cfg_welch(n, k, bands)
-    c.window = window
-    c.hop = n // 2 if window == cs.WINDOW_HANN else n
-    c.frames_per_epoch = k
-    return c
-
-
-def _zeros(shape, dtype):
-    return torch.zeros(shape, dtype=dtype, device=DEV)
-
-
-def _cfar(s, cfg, iq_t, E, outs=None):
-    """One CFAR launch over E epochs with `spectrum`, the mask and band_bins written; returns the device tensors."""
-    N, nb = cfg.fft_len, cfg.n_bands
-    if outs is None:
-        outs = {"features": _zeros((E, nb), torch.float32), "decision": _zeros((E,), torch.int32), "occupancy": _zeros((E, nb), torch.uint8),
-                "spectrum": _zeros((E, N), torch.float32), "mask": _zeros((E, N // 32), torch.int32), "band_bins": _zeros((E, nb), torch.int32)}
-    o = {"features": outs["features"].data_ptr(), "ann_out": 0, "decision": outs["decision"].data_ptr(),
-         "occupancy": outs["occupancy"].data_ptr(), "spectrum": outs["spectrum"].data_ptr()}
-    s.run_device_cfar(iq_t.data_ptr(), E, N, o, mask_ptr=outs["mask"].data_ptr(), band_bins_ptr=outs["band_bins"].data_ptr())
-    return outs
-
-
-class _Out:
-    """The fused mask, the fused rows and the headers of R fused rows on the device, each with PAD bytes behind it, all filled with 0xFF
-    first so that whatever the kernel skipped, or wrote past the end, shows."""
+class _Out(sgpu.Padded):
+    """The fused mask, the fused rows and the headers of R fused rows on the device, each with 0xFF bytes behind it (stage_gpu.Padded)."""
 
     def __init__(self, R, n):
         self.R, self.n = R, n
-        self.mask = torch.full((R * n // 8 + PAD,), 255, dtype=torch.uint8, device=DEV)
-        self.spec = torch.full((R * n * 4 + PAD,), 255, dtype=torch.uint8, device=DEV)
-        self.rows = torch.full((R * 16 + PAD,), 255, dtype=torch.uint8, device=DEV)
+        super().__init__(mask=R * n // 8, spec=R * n * 4, rows=R * 16)
 
     def host(self):
         """(mask words [R][n / 32] uint32, fused rows [R][n] float32, headers [R]); the three as bytes in .raw."""
-        torch.cuda.synchronize()
-        R, n = self.R, self.n
-        m, sp, ro = self.mask.cpu().numpy(), self.spec.cpu().numpy(), self.rows.cpu().numpy()
-        self.pads = (m[R * n // 8:], sp[R * n * 4:], ro[R * 16:])
-        self.raw = (m[: R * n // 8].tobytes(), sp[: R * n * 4].tobytes(), ro[: R * 16].tobytes())
-        return (np.frombuffer(self.raw[0], np.uint32).reshape(R, n // 32), np.frombuffer(self.raw[1], np.float32).reshape(R, n),
+        payload = super().host()
+        self.raw = tuple(payload[name].tobytes() for name in ("mask", "spec", "rows"))
+        return (np.frombuffer(self.raw[0], np.uint32).reshape(self.R, self.n // 32), np.frombuffer(self.raw[1], np.float32).reshape(self.R, self.n),
                 np.frombuffer(self.raw[2], cs.FUSE_ROW_DTYPE))
-
-    def pads_untouched(self):
-        return all((p == 255).all() for p in self.pads)
 
 
 def _upload(det, P):
-    return (None if det is None else torch.from_numpy(fu.pack_mask(det).view(np.int32)).to(DEV),
-            None if P is None else torch.from_numpy(np.ascontiguousarray(P, np.float32)).to(DEV))
+    return None if det is None else sgpu.upload_mask(det), None if P is None else sgpu.upload_rows(P)
 
 
 def _run(s, mask_t, spec_t, E, q, n, out=None, want=(True, True, True)):
@@ -128,7 +95,7 @@ def test_shapes_against_twin(built, n):
     """Every (M, G, T), every weight set, VOTE at k = 1, the majority and n_active (with and without the spectrum), SOFT at the four
     windows (the last fills 2 (g + W) + 1 = N - 1) and three alphas (with and without the masks)."""
     rng = np.random.default_rng(n)
-    s = cs.Sensor(_cfg(n, cs.WINDOW_RECT, 10))
+    s = cs.Sensor(sgpu.cfg(n, cs.WINDOW_RECT, 10))
     for M, G, T in ((1, 1, 1), (2, 1, 3), (3, 2, 1), (32, 1, 2), (5, 2, 3)):
         E = M * G * T
         det, P = _batch(rng, E, n)
@@ -152,7 +119,7 @@ def test_null_outputs_are_left_alone(built):
     rng = np.random.default_rng(77)
     det, P = _batch(rng, M * G * T, n)
     mask_t, spec_t = _upload(det, P)
-    s = cs.Sensor(_cfg(n, cs.WINDOW_RECT, 10))
+    s = cs.Sensor(sgpu.cfg(n, cs.WINDOW_RECT, 10))
     w = fu.equal_gain(M)
     for q in (_params(fu.VOTE, M, T, w, votes=2), _params(fu.SOFT, M, T, w, guard=G_, train=W_, alpha=1.5)):
         full = _run(s, mask_t, spec_t, det.shape[0], q, n)
@@ -182,7 +149,7 @@ def test_inactive_members_are_skipped(built, n):
         if m not in keep:
             det4[:, m], P4[:, m] = True, np.nan
     det, P = det4.reshape(-1, n), P4.reshape(-1, n)
-    s = cs.Sensor(_cfg(n, cs.WINDOW_RECT, 10))
+    s = cs.Sensor(sgpu.cfg(n, cs.WINDOW_RECT, 10))
     mask_t, spec_t = _upload(det, P)
     mask_s, spec_s = _upload(*small)
     for rule, kw in ((fu.VOTE, {"votes": 2}), (fu.SOFT, {"guard": G_, "train": W_, "alpha": 1.2})):
@@ -206,7 +173,7 @@ def test_strong_neighbour(built, n):
     batches = ([(5, -1, True), (259, -1, False), (200, +1, False), (331, +1, True)], [(5, -1, False), (331, +1, False)],
                [(n - 7, +1, True), (259, +1, True)], [(n - 7, +1, False), (200, -1, True)])
     w = rng.uniform(0.2, 1.0, M).astype(np.float32)
-    s = cs.Sensor(_cfg(n, cs.WINDOW_RECT, 10))
+    s = cs.Sensor(sgpu.cfg(n, cs.WINDOW_RECT, 10))
     for batch in batches:
         P = rng.gamma(10.0, 1e-4, (E, n))
         for k, side, far in batch:
@@ -230,7 +197,7 @@ def test_cut_independence(built):
     rng = np.random.default_rng(40)
     det, P = _batch(rng, M * G * T, n)
     mask_t, spec_t = _upload(det, P)
-    s = cs.Sensor(_cfg(n, cs.WINDOW_RECT, 10))
+    s = cs.Sensor(sgpu.cfg(n, cs.WINDOW_RECT, 10))
     w = rng.uniform(0.1, 1.0, M).astype(np.float32)
     for rule, kw in ((fu.VOTE, {"votes": 2}), (fu.SOFT, {"guard": G_, "train": W_, "alpha": 1.3})):
         whole = _run(s, mask_t, spec_t, det.shape[0], _params(rule, M, T, w, **kw), n)
@@ -261,7 +228,7 @@ def test_identity_and_chain(built):
     crn_channels_device with n_epochs = 12: the same bytes as those stages run on the twin's fused arrays."""
     n = 1024
     rng = np.random.default_rng(5)
-    s = cs.Sensor(_cfg(n, cs.WINDOW_RECT, 10))
+    s = cs.Sensor(sgpu.cfg(n, cs.WINDOW_RECT, 10))
     det, P = _batch(rng, 7, n)
     mask_t, spec_t = _upload(det, P)
     out = _run(s, mask_t, spec_t, 7, _params(fu.VOTE, 1, 7, [1.0], votes=1), n)
@@ -305,12 +272,12 @@ def test_against_the_sensing_kernels_ca_detector(built):
     row value, and the rounding of alpha / 2W)."""
     import signals
     n, k, E = 512, 10, 64
-    cfg = _cfg(n, cs.WINDOW_RECT, k)
+    cfg = sgpu.cfg(n, cs.WINDOW_RECT, k)
     iq, _ = signals.make_epochs(cfg, E, seed=512)
     s = cs.Sensor(cfg)
     alpha = cs.cfar_alpha(1e-2, k, W_)
     s.set_cfar(G_, W_, alpha, 1)
-    outs = _cfar(s, cfg, torch.from_numpy(iq).to(DEV), E)
+    outs = sgpu.cfar_launch(s, cfg, torch.from_numpy(iq).to(DEV), E)
     q = _params(fu.SOFT, 1, E, [1.0], guard=G_, train=W_, alpha=alpha)
     out = _run(s, None, outs["spectrum"], E, q, n)
     words, F, rows = out.host()
@@ -354,8 +321,8 @@ def test_end_to_end_swept_emitter(built):
     the fused false alarms in the reference band stay within 15 % of pfa x trials plus 4 binomial standard deviations."""
     n, k, M, T = E2E["n"], E2E["k"], E2E["members"], E2E["eps"]
     E = M * T
-    cfg = _cfg(n, cs.WINDOW_RECT, k)
-    iq_t = _zeros((cs.samples_needed(cfg, E) * 2,), torch.float32)
+    cfg = sgpu.cfg(n, cs.WINDOW_RECT, k)
+    iq_t = sgpu.zeros((cs.samples_needed(cfg, E) * 2,), torch.float32)
     truth_t = torch.full((E,), -1, dtype=torch.int32, device=DEV)
     sc = cs.SynthCfg()
     sc.seed, sc.noise_power, sc.signal_rms = E2E["seed"], E2E["noise_power"], E2E["signal_rms"]
@@ -363,7 +330,7 @@ def test_end_to_end_swept_emitter(built):
     s = cs.Sensor(cfg)
     s.synth_fill_device_ex(iq_t.data_ptr(), E, cs.samples_per_epoch(cfg), sc, truth_ptr=truth_t.data_ptr())
     s.set_cfar(G_, W_, cs.cfar_alpha(E2E["pfa"], k, W_), 1)
-    outs = _cfar(s, cfg, iq_t, E)
+    outs = sgpu.cfar_launch(s, cfg, iq_t, E)
     alpha = cs.cfar_alpha(E2E["pfa"], M * k, W_)
     w = fu.equal_gain(M)
     out = _run(s, outs["mask"], outs["spectrum"], E, _params(fu.SOFT, M, T, w, guard=G_, train=W_, alpha=alpha), n)
@@ -457,39 +424,26 @@ SPEED_RATIO = SPEED_MEASURED * 1.15 / 1.084
 
 
 def test_cost_next_to_the_cfar_launch(built):
-    """N = 4096, K = 10, rect, 64 bands, the 2.18 GB batch; the method of tests/test_channels_gpu.py's cost test: each timed window holds
-    R launches issued back to back behind one already queued, the arms alternate, 5 windows each after a warm-up, the best counts.  Arm A
+    """N = 4096, K = 10, rect, 64 bands, the 2.18 GB batch; the method of tests/stage_gpu.py (best_of_windows): each timed window holds
+    8 launches issued back to back behind one already queued, the arms alternate, 5 windows each after a warm-up, the best counts.  Arm A
     is the CFAR launch alone, arm B the same launch followed by crn_fuse_device on the same stream: SOFT, M = 4, G = 1, T = 1664, guard 2,
     train 16, all three outputs written.  VOTE (majority of 4), M = 32 (SOFT, T = 208) and the stage alone are measured the same way
     and printed with the GB/s of the stage's own bytes: M (4 N + N / 8) read and 4 N + N / 8 + 16 written per fused row."""
     n, k = 4096, 10
-    cfg = _cfg(n, cs.WINDOW_RECT, k, bands=64)
+    cfg = sgpu.cfg(n, cs.WINDOW_RECT, k, bands=64)
     E = 6656                                  # 6656 x 10 x 4096 x 8 B = 2.18 GB
-    gen = torch.Generator(device=DEV)
-    gen.manual_seed(5)
-    iq_t = torch.randn(E * k * n * 2, generator=gen, device=DEV, dtype=torch.float32)
+    iq_t = sgpu.noise_batch(E, k, n)
     s = cs.Sensor(cfg)
     s.set_cfar(G_, W_, cs.cfar_alpha(1e-3, k, W_), 1)
-    outs = _cfar(s, cfg, iq_t, E)
+    outs = sgpu.cfar_launch(s, cfg, iq_t, E)
     torch.cuda.synchronize()
-    R = 8
     runs = {"soft": (4, _params(fu.SOFT, 4, E // 4, fu.equal_gain(4), guard=G_, train=W_, alpha=cs.cfar_alpha(1e-3, 4 * k, W_))),
             "vote": (4, _params(fu.VOTE, 4, E // 4, fu.equal_gain(4), votes=2)),
             "soft32": (32, _params(fu.SOFT, 32, E // 32, fu.equal_gain(32), guard=G_, train=W_, alpha=cs.cfar_alpha(1e-3, 32 * k, W_)))}
     bufs = {name: _Out(E // M, n) for name, (M, _) in runs.items()}
 
-    def timed(fn):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        fn()
-        a.record()
-        for _ in range(R):
-            fn()
-        b.record()
-        b.synchronize()
-        return a.elapsed_time(b) / R
-
     def arm_a():
-        _cfar(s, cfg, iq_t, E, outs=outs)
+        sgpu.cfar_launch(s, cfg, iq_t, E, outs=outs)
 
     def stage(name):
         _run(s, outs["mask"], outs["spectrum"], E, runs[name][1], n, out=bufs[name])
@@ -499,18 +453,10 @@ def test_cost_next_to_the_cfar_launch(built):
         stage(name)
     arms = {"A": arm_a, "B soft": arm_b, "B vote": lambda: arm_b("vote"), "B soft32": lambda: arm_b("soft32"),
             "alone soft": lambda: stage("soft"), "alone vote": lambda: stage("vote"), "alone soft32": lambda: stage("soft32")}
-    for fn in arms.values():
-        fn()
-    torch.cuda.synchronize()
-    times = {name: [] for name in arms}
-    for _ in range(5):
-        for name, fn in arms.items():
-            times[name].append(timed(fn))
+    times = sgpu.best_of_windows(arms)
     rows = bufs["soft"].host()[2]
     s.close()
     best = {name: min(v) for name, v in times.items()}
-    for name, v in times.items():
-        print(f"ms per launch, {name}:", " ".join(f"{x:.4f}" for x in v))
     nbytes = E * k * n * 8
     print(f"N=4096 K=10 rect 64 bands, {E} epochs ({nbytes / 1e9:.2f} GB), spectrum written: arm A (CFAR launch alone) {best['A']:.4f} ms "
           f"({nbytes / best['A'] / 1e6:.0f} GB/s of input)")

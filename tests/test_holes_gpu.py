@@ -17,46 +17,21 @@ import holes_f64 as hf
 pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
-DEV = "cuda"
+import stage_gpu as sgpu        # noqa: E402  (needs torch)
+from stage_gpu import DEV       # noqa: E402
+
 G_, W_ = 2, 16
 SIZES = (512, 1024, 2048, 4096)
-PAD = 256                      # bytes of 0xFF kept behind every output array
 DEFAULTS = {"guard": 0, "min_age": 1, "min_width": 1, "max_holes": 16, "avg_epochs": 1}
 
 
-def _cfg(n, window, k, bands=None):
-    c = cs.cfg_energy_scaled(n) if bands is None else cs.cfg_welch(n, k, bands)
-    c.window = window
-    c.hop = n // 2 if window == cs.WINDOW_HANN else n
-    c.frames_per_epoch = k
-    return c
-
-
-def _zeros(shape, dtype):
-    return torch.zeros(shape, dtype=dtype, device=DEV)
-
-
-def _cfar(s, cfg, iq_t, E, outs=None):
-    """One CFAR launch over E epochs with `spectrum`, the mask and band_bins written; returns the device tensors."""
-    N, nb = cfg.fft_len, cfg.n_bands
-    if outs is None:
-        outs = {"features": _zeros((E, nb), torch.float32), "decision": _zeros((E,), torch.int32), "occupancy": _zeros((E, nb), torch.uint8),
-                "spectrum": _zeros((E, N), torch.float32), "mask": _zeros((E, N // 32), torch.int32), "band_bins": _zeros((E, nb), torch.int32)}
-    o = {"features": outs["features"].data_ptr(), "ann_out": 0, "decision": outs["decision"].data_ptr(),
-         "occupancy": outs["occupancy"].data_ptr(), "spectrum": outs["spectrum"].data_ptr()}
-    s.run_device_cfar(iq_t.data_ptr(), E, N, o, mask_ptr=outs["mask"].data_ptr(), band_bins_ptr=outs["band_bins"].data_ptr())
-    return outs
-
-
-class _Out:
-    """d_age, the headers, the holes and d_free_mask of a batch on the device, each with PAD bytes behind it, all filled with 0xFF first so
-    that whatever the kernels skipped, or wrote past the end, shows.  The workspace is exactly the size the library asks for."""
+class _Out(sgpu.Padded):
+    """d_age, the headers, the holes and d_free_mask of a batch on the device, each with 0xFF bytes behind it (stage_gpu.Padded).  The
+    workspace is exactly the size the library asks for."""
 
     def __init__(self, E, n_streams, n, eps, q):
         self.S, self.n, self.mh = n_streams, n, q["max_holes"]
-        self.sizes = {"age": n_streams * n * 4, "streams": n_streams * 32, "holes": n_streams * self.mh * 32, "free": n_streams * n // 8}
-        for name, nb in self.sizes.items():
-            setattr(self, name, torch.full((nb + PAD,), 255, dtype=torch.uint8, device=DEV))
+        super().__init__(age=n_streams * n * 4, streams=n_streams * 32, holes=n_streams * self.mh * 32, free=n_streams * n // 8)
         self.ws_bytes = cs.holes_workspace_bytes(E, eps, **q)
         self.ws = torch.full((self.ws_bytes,), 255, dtype=torch.uint8, device=DEV)
 
@@ -65,17 +40,9 @@ class _Out:
         self.age[: raw.size] = torch.from_numpy(raw.copy()).to(DEV)
 
     def host(self):
-        torch.cuda.synchronize()
-        raw = {name: getattr(self, name).cpu().numpy() for name in self.sizes}
-        self.pads = [raw[name][nb:] for name, nb in self.sizes.items()]
-        self.raw = {name: raw[name][:nb] for name, nb in self.sizes.items()}
-        return (np.frombuffer(self.raw["age"].tobytes(), np.int32).reshape(self.S, self.n),
-                np.frombuffer(self.raw["free"].tobytes(), np.uint32).reshape(self.S, self.n // 32),
-                np.frombuffer(self.raw["streams"].tobytes(), np.dtype(cs.HOLE_STREAM_DTYPE)),
-                np.frombuffer(self.raw["holes"].tobytes(), np.dtype(cs.HOLE_DTYPE)).reshape(self.S, self.mh))
-
-    def pads_untouched(self):
-        return all((p == 255).all() for p in self.pads)
+        super().host()
+        return (self.view("age", np.int32, (self.S, self.n)), self.view("free", np.uint32, (self.S, self.n // 32)),
+                self.view("streams", cs.HOLE_STREAM_DTYPE), self.view("holes", cs.HOLE_DTYPE, (self.S, self.mh)))
 
 
 def _run(s, mask_t, spec_t, E, eps, q, first=True, out=None, holes=True, free=True):
@@ -88,7 +55,7 @@ def _run(s, mask_t, spec_t, E, eps, q, first=True, out=None, holes=True, free=Tr
 
 
 def _upload(det, P):
-    return (torch.from_numpy(hf.pack_mask(det).view(np.int32)).to(DEV), None if P is None else torch.from_numpy(np.ascontiguousarray(P, np.float32)).to(DEV))
+    return sgpu.upload_mask(det), None if P is None else sgpu.upload_rows(P)
 
 
 def _check(s, det, P, eps, what, age0=None, holes=True, free=True, uploaded=None, **kw):
@@ -148,7 +115,7 @@ def test_shapes_against_twin(built, n, S, T):
     rng = np.random.default_rng(n + 31 * S + T)
     E = S * T
     P = _rows(rng, E, n)
-    s = cs.Sensor(_cfg(n, cs.WINDOW_RECT, 10))
+    s = cs.Sensor(sgpu.cfg(n, cs.WINDOW_RECT, 10))
     worst, most = 0.0, 0
     masks = [(f"density {d}", rng.random((E, n)) < d) for d in (0.0, 0.002, 0.5, 1.0)] + [("edges", _edge_mask(E, n))]
     for name, det in masks:
@@ -168,7 +135,7 @@ def test_carry_and_null_outputs(built, n):
     det = rng.random((S * T, n)) < 0.004
     det[:, 100:140] = False                                   # bins no epoch of the batch blocks: their age is the carry's + T
     P = _rows(rng, S * T, n)
-    s = cs.Sensor(_cfg(n, cs.WINDOW_RECT, 10))
+    s = cs.Sensor(sgpu.cfg(n, cs.WINDOW_RECT, 10))
     q = {"guard": 1, "min_age": 8, "min_width": 4, "max_holes": 8, "avg_epochs": 8}
     fresh, _ = _check(s, det, P, T, "first after 0xFF garbage", **q)
     zeroed, _ = _check(s, det, P, T, "a zeroed d_age", age0=np.zeros((S, n), np.int32), **q)
@@ -218,7 +185,7 @@ def test_strong_neighbour(built, n):
     det = np.ones((T, n), bool)
     for lo, w in spans:
         det[:, (lo + np.arange(w)) % n] = False
-    s = cs.Sensor(_cfg(n, cs.WINDOW_RECT, 10))
+    s = cs.Sensor(sgpu.cfg(n, cs.WINDOW_RECT, 10))
     for inside in (False, True):
         P = rng.gamma(10.0, 1e-4, (T, n))
         loud = {}
@@ -257,7 +224,7 @@ def test_cut_independence(built, n):
     det[:, 50:90] = rng.random((S * T, 1)) < 0.05                # a channel that comes and goes
     P = _rows(rng, S * T, n)
     q = {"guard": 2, "min_age": 8, "min_width": 8, "max_holes": 16, "avg_epochs": 8}
-    s = cs.Sensor(_cfg(n, cs.WINDOW_RECT, 10))
+    s = cs.Sensor(sgpu.cfg(n, cs.WINDOW_RECT, 10))
     mask_t, spec_t = _upload(det, P)
     whole, _ = _check(s, det, P, T, "whole", uploaded=(mask_t, spec_t), **q)
     for cuts in ([1], [37], [64], [128], [64, 128], [1, 37, 64, 128, 193], [199]):
@@ -293,7 +260,7 @@ def test_free_mask_feeds_the_channel_stage(built):
     iq, _ = signals.make_epochs(cfg, E, seed=n + 14)
     s = cs.Sensor(cfg)
     s.set_cfar(G_, W_, cs.cfar_alpha(1e-2, k, W_), 1)
-    outs = _cfar(s, cfg, torch.from_numpy(iq).to(DEV), E)
+    outs = sgpu.cfar_launch(s, cfg, torch.from_numpy(iq).to(DEV), E)
     q = {**DEFAULTS, "guard": 1, "min_age": 2}
     out = _run(s, outs["mask"], outs["spectrum"], E, T, q)
     age, free, st, holes = out.host()
@@ -334,8 +301,8 @@ def test_end_to_end_markov_chain(built):
     pooled (the bar the host simulation justifies).  Every piece equals the twin on the kernel's own mask."""
     n, k, S, T, piece = E2E["n"], E2E["k"], E2E["n_streams"], E2E["eps"], E2E["piece"]
     E = S * T
-    cfg = _cfg(n, cs.WINDOW_RECT, k)
-    iq_t = _zeros((cs.samples_needed(cfg, E) * 2,), torch.float32)
+    cfg = sgpu.cfg(n, cs.WINDOW_RECT, k)
+    iq_t = sgpu.zeros((cs.samples_needed(cfg, E) * 2,), torch.float32)
     truth_t = torch.full((E,), -1, dtype=torch.int32, device=DEV)
     sc = cs.SynthCfg()
     sc.seed, sc.noise_power, sc.signal_rms = E2E["seed"], E2E["noise_power"], E2E["signal_rms"]
@@ -343,7 +310,7 @@ def test_end_to_end_markov_chain(built):
     s = cs.Sensor(cfg)
     s.synth_fill_device_ex(iq_t.data_ptr(), E, cs.samples_per_epoch(cfg), sc, truth_ptr=truth_t.data_ptr())
     s.set_cfar(G_, W_, cs.cfar_alpha(E2E["pfa"], k, W_), 1)
-    outs = _cfar(s, cfg, iq_t, E)
+    outs = sgpu.cfar_launch(s, cfg, iq_t, E)
     truth = truth_t.cpu().numpy().reshape(S, T)
     det = hf.unpack_mask(outs["mask"].cpu().numpy().view(np.uint32), n).reshape(S, T, n)
     q = {"guard": E2E["guard"], "min_age": E2E["min_age"], "min_width": E2E["min_width"], "max_holes": 16, "avg_epochs": 8}
@@ -424,45 +391,25 @@ SPEED_RATIO = 1.158
 
 
 def test_cost_next_to_the_cfar_launch(built):
-    """N = 4096, K = 10, rect, 64 bands, the 2.18 GB batch; the method of tests/test_channels_gpu.py's cost test: each timed window holds
+    """N = 4096, K = 10, rect, 64 bands, the 2.18 GB batch; the method of tests/stage_gpu.py (best_of_windows): each timed window holds
     8 launches issued back to back behind one already queued, the arms alternate, 5 windows each after a warm-up, the best counts.  Arm A
     is the CFAR launch alone, arm B the same launch followed by crn_holes_device on the same stream with all outputs, guard 2, min_age 8,
     min_width 8, max_holes 16, avg_epochs 8: one stream of 6656 epochs, and 64 streams of 104.  Both layouts are held to the bar; the
     stage alone is measured the same way and printed."""
     n, k = 4096, 10
-    cfg = _cfg(n, cs.WINDOW_RECT, k, bands=64)
+    cfg = sgpu.cfg(n, cs.WINDOW_RECT, k, bands=64)
     E = 6656                                  # 6656 x 10 x 4096 x 8 B = 2.18 GB
-    gen = torch.Generator(device=DEV)
-    gen.manual_seed(5)
-    iq_t = torch.randn(E * k * n * 2, generator=gen, device=DEV, dtype=torch.float32)
-    # the traffic of the segments cost test: tones over unit noise in two epochs of three
-    t = torch.arange(n, device=DEV, dtype=torch.float32)
-    frames = iq_t.view(E, k, n, 2)
-    for j, b in enumerate((300, 301, 302, 303, 1600, 1601, 1602, 3000)):
-        ph = 2 * np.pi * ((b * t) % n) / n
-        sel = slice(j % 3, E, 3)
-        frames[sel, :, :, 0] += 0.3 * torch.cos(ph)
-        frames[sel, :, :, 1] += 0.3 * torch.sin(ph)
+    # the traffic of every cost test here: tones over unit noise in two epochs of three
+    iq_t = sgpu.add_tones(sgpu.noise_batch(E, k, n), E, k, n)
     s = cs.Sensor(cfg)
     s.set_cfar(G_, W_, cs.cfar_alpha(1e-3, k, W_), 1)
-    outs = _cfar(s, cfg, iq_t, E)
+    outs = sgpu.cfar_launch(s, cfg, iq_t, E)
     q = {"guard": 2, "min_age": 8, "min_width": 8, "max_holes": 16, "avg_epochs": 8}
     one, many = _Out(E, 1, n, E, q), _Out(E, 64, n, 104, q)
     torch.cuda.synchronize()
-    R = 8
-
-    def timed(fn):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        fn()
-        a.record()
-        for _ in range(R):
-            fn()
-        b.record()
-        b.synchronize()
-        return a.elapsed_time(b) / R
 
     def arm_a():
-        _cfar(s, cfg, iq_t, E, outs=outs)
+        sgpu.cfar_launch(s, cfg, iq_t, E, outs=outs)
 
     def stage(out, eps):
         _run(s, outs["mask"], outs["spectrum"], E, eps, q, first=True, out=out)
@@ -472,20 +419,12 @@ def test_cost_next_to_the_cfar_launch(built):
         stage(out, eps)
     arms = {"A": arm_a, "B one stream": arm_b, "B 64 streams": lambda: arm_b(many, 104), "alone one stream": lambda: stage(one, E),
             "alone 64 streams": lambda: stage(many, 104)}
-    for fn in arms.values():
-        fn()
-    torch.cuda.synchronize()
-    times = {name: [] for name in arms}
-    for _ in range(5):
-        for name, fn in arms.items():
-            times[name].append(timed(fn))
+    times = sgpu.best_of_windows(arms)
     g_one, g_many = one.host(), many.host()
     assert one.pads_untouched() and many.pads_untouched()
     det = hf.unpack_mask(outs["mask"].cpu().numpy().view(np.uint32), n)
     s.close()
     best = {name: min(v) for name, v in times.items()}
-    for name, v in times.items():
-        print(f"ms per launch, {name}:", " ".join(f"{x:.4f}" for x in v))
     nbytes = E * k * n * 8
     print(f"N=4096 K=10 rect 64 bands, {E} epochs ({nbytes / 1e9:.2f} GB), spectrum written: arm A (CFAR launch alone) {best['A']:.4f} ms "
           f"({nbytes / best['A'] / 1e6:.0f} GB/s of input)")

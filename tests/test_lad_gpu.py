@@ -18,18 +18,11 @@ import lad_f64 as lf
 pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
-DEV = "cuda"
+import stage_gpu as sgpu        # noqa: E402  (needs torch)
+from stage_gpu import DEV       # noqa: E402
+
 G_, W_ = 2, 16
-PAD = 256                      # bytes of 0xFF kept behind every output array
 Q10 = lc.params(10)
-
-
-def _cfg(n, k=10, bands=None):
-    c = cs.cfg_energy_scaled(n) if bands is None else cs.cfg_welch(n, k, bands)
-    c.window = cs.WINDOW_RECT
-    c.hop = n
-    c.frames_per_epoch = k
-    return c
 
 
 @functools.lru_cache(maxsize=None)
@@ -47,27 +40,16 @@ def _slice(want, rows):
     return tuple(w[rows] for w in want)
 
 
-class _Out:
-    """The mask, the headers and the floors of a batch on the device, each with PAD bytes behind it, all filled with 0xFF first so that
-    whatever the kernel skipped, or wrote past the end, shows."""
+class _Out(sgpu.Padded):
+    """The mask, the headers and the floors of a batch on the device, each with 0xFF bytes behind it (stage_gpu.Padded)."""
 
     def __init__(self, E, n, n_blocks):
         self.E, self.n, self.nb = E, n, n_blocks
-        self.sizes = {"mask": E * n // 8, "rows": E * 32, "floor": E * n_blocks * 4}
-        for name, nb in self.sizes.items():
-            setattr(self, name, torch.full((nb + PAD,), 255, dtype=torch.uint8, device=DEV))
+        super().__init__(mask=E * n // 8, rows=E * 32, floor=E * n_blocks * 4)
 
     def host(self):
-        torch.cuda.synchronize()
-        raw = {name: getattr(self, name).cpu().numpy() for name in self.sizes}
-        self.pads = [raw[name][nb:] for name, nb in self.sizes.items()]
-        self.raw = {name: raw[name][:nb] for name, nb in self.sizes.items()}
-        return (np.frombuffer(self.raw["mask"].tobytes(), np.uint32).reshape(self.E, self.n // 32),
-                np.frombuffer(self.raw["rows"].tobytes(), np.dtype(cs.LAD_ROW_DTYPE)),
-                np.frombuffer(self.raw["floor"].tobytes(), np.float32).reshape(self.E, self.nb))
-
-    def pads_untouched(self):
-        return all((p == 255).all() for p in self.pads)
+        super().host()
+        return self.view("mask", np.uint32, (self.E, self.n // 32)), self.view("rows", cs.LAD_ROW_DTYPE), self.view("floor", np.float32, (self.E, self.nb))
 
 
 def _launch(s, spec_t, E, n_blocks, init_percent, q, out, or_ptr=0, mask=True, rows=True, floor=True):
@@ -76,16 +58,12 @@ def _launch(s, spec_t, E, n_blocks, init_percent, q, out, or_ptr=0, mask=True, r
     return out
 
 
-def _upload(P):
-    return torch.from_numpy(np.ascontiguousarray(P, np.float32)).to(DEV)
-
-
 def _check(s, P, n_blocks, init_percent, what, q=Q10, want=None, or_mask=None, spec_t=None):
     """One launch with every output against the twin.  Returns (the outputs, the number of undecided rows)."""
     E, n = P.shape
-    spec_t = _upload(P) if spec_t is None else spec_t
+    spec_t = sgpu.upload_rows(P) if spec_t is None else spec_t
     out = _Out(E, n, n_blocks)
-    or_t = None if or_mask is None else torch.from_numpy(lf.pack_mask(or_mask).view(np.int32)).to(DEV)
+    or_t = None if or_mask is None else sgpu.upload_mask(or_mask)
     _launch(s, spec_t, E, n_blocks, init_percent, q, out, or_ptr=0 if or_t is None else or_t.data_ptr())
     got = out.host()
     assert out.pads_untouched(), (what, "memory behind an output array was written")
@@ -102,8 +80,8 @@ def test_shapes_against_twin(built, n, E):
     other end, E = 1 the row with one bin 90 dB over the floor."""
     rows = {1: slice(10, 11), 3: slice(lc.E_MAX - 3, lc.E_MAX), 65: slice(0, lc.E_MAX)}[E]
     P = _batch(n)[rows]
-    spec_t = _upload(P)
-    s = cs.Sensor(_cfg(n))
+    spec_t = sgpu.upload_rows(P)
+    s = cs.Sensor(sgpu.cfg(n))
     skipped = 0
     for n_blocks in lc.blocks_allowed(n):
         for ip in lc.INIT_PERCENTS:
@@ -121,7 +99,7 @@ def test_shapes_against_twin(built, n, E):
 def test_noise_rows_of_other_seeds(built, n):
     """Gamma(K) noise for K = 1 and 10 with the factors of each K, 16 rows each, on the largest number of blocks."""
     rng = np.random.default_rng(n + 17)
-    s = cs.Sensor(_cfg(n))
+    s = cs.Sensor(sgpu.cfg(n))
     skipped = 0
     for k in (1, 10):
         P = rng.gamma(float(k), lc.MEAN / k, (16, n)).astype(np.float32)
@@ -141,7 +119,7 @@ def test_lower_all_ones(built, n):
     for e, k in enumerate((0, n - 1, n // 2 + 7)):
         P[e, k] = 2.0 * lc.MEAN
     P = P.astype(np.float32)
-    s = cs.Sensor(_cfg(n))
+    s = cs.Sensor(sgpu.cfg(n))
     for n_blocks in (1, 2):
         got, skipped = _check(s, P, n_blocks, 10, f"lower all ones N={n} n_blocks={n_blocks}", q=q)
         assert skipped == 0
@@ -155,13 +133,13 @@ def test_optional_arguments(built, n):
     """d_or_mask given, NULL, and the same address as d_bin_mask; each output NULL in turn; n_epochs = 0 touches nothing."""
     E = 14                                                     # one row of every kind
     P = _batch(n)[:E]
-    spec_t = _upload(P)
+    spec_t = sgpu.upload_rows(P)
     n_blocks, ip = lc.blocks_allowed(n)[-1], 10
     want = _slice(_twin(n, n_blocks, ip), slice(0, E))
     rng = np.random.default_rng(n + 1)
     om = rng.random((E, n)) < 0.01
     om[:, [0, 31, 32, n - 1]] = True
-    s = cs.Sensor(_cfg(n))
+    s = cs.Sensor(sgpu.cfg(n))
     plain, _ = _check(s, P, n_blocks, ip, "no d_or_mask", want=want, spec_t=spec_t)
     with_or, _ = _check(s, P, n_blocks, ip, "d_or_mask given", or_mask=om, spec_t=spec_t)
     assert with_or[0].tobytes() == (plain[0] | lf.pack_mask(om)).tobytes() and with_or[2].tobytes() == plain[2].tobytes()
@@ -196,9 +174,9 @@ def test_cut_independence(built, n):
     """65 rows in one call against the same rows cut at 1, at 64, and row by row: the same bytes."""
     E = lc.E_MAX
     P = _batch(n)
-    spec_t = _upload(P)
+    spec_t = sgpu.upload_rows(P)
     n_blocks = lc.blocks_allowed(n)[-1]
-    s = cs.Sensor(_cfg(n))
+    s = cs.Sensor(sgpu.cfg(n))
     whole, _ = _check(s, P, n_blocks, 10, "whole", want=_twin(n, n_blocks, 10), spec_t=spec_t)
     for cuts in ([1], [64], list(range(1, E))):
         edges = [0] + cuts + [E]
@@ -216,8 +194,8 @@ def test_refusals_with_a_live_handle(built):
     """Every refusal of the header's list with a live handle; n_blocks is checked against the handle's fft_len."""
     n, E = 512, 4
     L = cs.lib()
-    s = cs.Sensor(_cfg(n))
-    spec_t = _upload(_batch(n)[:E])
+    s = cs.Sensor(sgpu.cfg(n))
+    spec_t = sgpu.upload_rows(_batch(n)[:E])
     out = _Out(E, n, 2)
     or_t = torch.zeros((E * n // 32,), dtype=torch.int32, device=DEV)
     inf, nan = float("inf"), float("nan")
@@ -248,8 +226,8 @@ def test_refusals_with_a_live_handle(built):
     s.close()
     # a 4096-point handle takes eight blocks, a 1024-point one four and not eight
     for n, ok, bad in ((4096, 8, 16), (1024, 4, 8)):
-        s = cs.Sensor(_cfg(n))
-        sp = _upload(_batch(n)[:1])
+        s = cs.Sensor(sgpu.cfg(n))
+        sp = sgpu.upload_rows(_batch(n)[:1])
         o = _Out(1, n, 8)
         for nb, want in ((ok, 0), (bad, cs.CRN_ERR_ARG)):
             q = cs.lad_params(nb, 10, **Q10)
@@ -273,7 +251,7 @@ def test_end_to_end_band_noise(built):
     overlaps the driven channel, and it covers at least 0.9 of it.  Every row equals the twin."""
     n, k, S, T = E2E["n"], E2E["k"], E2E["n_streams"], E2E["eps"]
     E = S * T
-    cfg = _cfg(n, k)
+    cfg = sgpu.cfg(n, k=k)
     iq_t = torch.zeros((cs.samples_needed(cfg, E) * 2,), dtype=torch.float32, device=DEV)
     truth_t = torch.full((E,), -1, dtype=torch.int32, device=DEV)
     sc = cs.SynthCfg()
@@ -282,13 +260,7 @@ def test_end_to_end_band_noise(built):
     s = cs.Sensor(cfg)
     s.synth_fill_device_ex(iq_t.data_ptr(), E, cs.samples_per_epoch(cfg), sc, truth_ptr=truth_t.data_ptr())
     s.set_cfar(G_, W_, cs.cfar_alpha(E2E["pfa"], k, W_), 1)
-    nb = cfg.n_bands
-    z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=DEV)      # noqa: E731
-    outs = {"features": z((E, nb), torch.float32), "decision": z((E,), torch.int32), "occupancy": z((E, nb), torch.uint8),
-            "spectrum": z((E, n), torch.float32), "mask": z((E, n // 32), torch.int32)}
-    s.run_device_cfar(iq_t.data_ptr(), E, n, {"features": outs["features"].data_ptr(), "ann_out": 0, "decision": outs["decision"].data_ptr(),
-                                              "occupancy": outs["occupancy"].data_ptr(), "spectrum": outs["spectrum"].data_ptr()},
-                      mask_ptr=outs["mask"].data_ptr())
+    outs = sgpu.cfar_launch(s, cfg, iq_t, E, band_bins=False)
     t_cme = cs.lad_factor(1e-2, k)
     q = {"t_cme": t_cme, "t_lower": cs.lad_factor(1e-2, k, t_cme), "t_upper": cs.lad_factor(1e-4, k, t_cme)}
     out = _launch(s, outs["spectrum"], E, 1, 10, q, _Out(E, n, 1))
@@ -338,47 +310,22 @@ SPEED_RATIO = 1.407
 
 
 def test_cost_next_to_the_cfar_launch(built):
-    """N = 4096, K = 10, rect, 64 bands, 6656 epochs; the method of tests/test_holes_gpu.py's cost test: each timed window holds 8
+    """N = 4096, K = 10, rect, 64 bands, 6656 epochs; the method of tests/stage_gpu.py (best_of_windows): each timed window holds 8
     launches issued back to back behind one already queued, the arms alternate, 5 windows each after a warm-up, the best counts.  Arm A
     is the CFAR launch alone, arm B the same launch followed by crn_lad_device on the same stream with all outputs, d_or_mask the CFAR
     mask, n_blocks = 8.  The stage alone is measured the same way and printed."""
     n, k = 4096, 10
-    cfg = _cfg(n, k, bands=64)
+    cfg = sgpu.cfg(n, k=k, bands=64)
     E = 6656                                  # 6656 x 10 x 4096 x 8 B = 2.18 GB
-    gen = torch.Generator(device=DEV)
-    gen.manual_seed(5)
-    iq_t = torch.randn(E * k * n * 2, generator=gen, device=DEV, dtype=torch.float32)
-    # the traffic of the segments cost test: tones over unit noise in two epochs of three
-    t = torch.arange(n, device=DEV, dtype=torch.float32)
-    frames = iq_t.view(E, k, n, 2)
-    for j, b in enumerate((300, 301, 302, 303, 1600, 1601, 1602, 3000)):
-        ph = 2 * np.pi * ((b * t) % n) / n
-        sel = slice(j % 3, E, 3)
-        frames[sel, :, :, 0] += 0.3 * torch.cos(ph)
-        frames[sel, :, :, 1] += 0.3 * torch.sin(ph)
+    # the traffic of every cost test here: tones over unit noise in two epochs of three
+    iq_t = sgpu.add_tones(sgpu.noise_batch(E, k, n), E, k, n)
     s = cs.Sensor(cfg)
     s.set_cfar(G_, W_, cs.cfar_alpha(1e-3, k, W_), 1)
-    nb = cfg.n_bands
-    z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=DEV)      # noqa: E731
-    outs = {"features": z((E, nb), torch.float32), "decision": z((E,), torch.int32), "occupancy": z((E, nb), torch.uint8),
-            "spectrum": z((E, n), torch.float32), "mask": z((E, n // 32), torch.int32), "band_bins": z((E, nb), torch.int32)}
-    o = {"features": outs["features"].data_ptr(), "ann_out": 0, "decision": outs["decision"].data_ptr(), "occupancy": outs["occupancy"].data_ptr(),
-         "spectrum": outs["spectrum"].data_ptr()}
+    outs = sgpu.cfar_outs(cfg, E)
     out = _Out(E, n, 8)
-    R = 8
-
-    def timed(fn):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        fn()
-        a.record()
-        for _ in range(R):
-            fn()
-        b.record()
-        b.synchronize()
-        return a.elapsed_time(b) / R
 
     def arm_a():
-        s.run_device_cfar(iq_t.data_ptr(), E, n, o, mask_ptr=outs["mask"].data_ptr(), band_bins_ptr=outs["band_bins"].data_ptr())
+        sgpu.cfar_launch(s, cfg, iq_t, E, outs=outs)
 
     def stage():
         _launch(s, outs["spectrum"], E, 8, 10, Q10, out, or_ptr=outs["mask"].data_ptr())
@@ -387,13 +334,7 @@ def test_cost_next_to_the_cfar_launch(built):
         arm_a()
         stage()
     arms = {"A": arm_a, "B": arm_b, "alone": stage}
-    for fn in arms.values():
-        fn()
-    torch.cuda.synchronize()
-    times = {name: [] for name in arms}
-    for _ in range(5):
-        for name, fn in arms.items():
-            times[name].append(timed(fn))
+    times = sgpu.best_of_windows(arms)
     got = out.host()
     assert out.pads_untouched()
     # the stage computed what the definition says: every 16th row against the twin on the kernel's own inputs
@@ -403,8 +344,6 @@ def test_cost_next_to_the_cfar_launch(built):
     s.close()
     skipped = lf.compare(got[0][pick], got[1][pick], got[2][pick], lf.run(P, 8, 10, or_mask=cfar, **Q10), "cost batch")
     best = {name: min(v) for name, v in times.items()}
-    for name, v in times.items():
-        print(f"ms per launch, {name}:", " ".join(f"{x:.4f}" for x in v))
     nbytes = E * k * n * 8
     print(f"N=4096 K=10 rect 64 bands, {E} epochs ({nbytes / 1e9:.2f} GB), spectrum written: arm A (CFAR launch alone) {best['A']:.4f} ms "
           f"({nbytes / best['A'] / 1e6:.0f} GB/s of input); B / A = {best['B'] / best['A']:.4f}; crn_lad_device alone {best['alone'] * 1e3:.1f} us; "

@@ -9,12 +9,12 @@ import numpy as np
 import pytest
 
 import crnsense as cs
-import segments_f64 as sg
 
 pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
-DEV = "cuda"
+import stage_gpu as sgpu        # noqa: E402  (needs torch)
+from stage_gpu import DEV       # noqa: E402
 MAX_OUT = (4, 16)        # 4: fewer slots than some rows have runs
 
 
@@ -71,9 +71,9 @@ def test_holes_of_a_mask_are_the_segments_of_its_complement(built, n):
     E = free.shape[0]
     P = np.random.default_rng(n + 1).gamma(10.0, 1e-4, (E, n)).astype(np.float32)
     assert (P > 0).all()
-    spec_t = torch.from_numpy(P).to(DEV)
-    blocked_t = torch.from_numpy(sg.pack_mask(~free).view(np.int32)).to(DEV)     # what crn_holes_device reads
-    free_t = torch.from_numpy(sg.pack_mask(free).view(np.int32)).to(DEV)         # what crn_segments_device reads
+    spec_t = sgpu.upload_rows(P)
+    blocked_t = sgpu.upload_mask(~free)     # what crn_holes_device reads
+    free_t = sgpu.upload_mask(free)         # what crn_segments_device reads
     widths = [_runs(f) for f in free]
     s = cs.Sensor(cs.cfg_energy_scaled(n))
     stored = 0

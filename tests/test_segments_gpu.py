@@ -15,34 +15,17 @@ import segments_f64 as sg
 pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
-DEV = "cuda"
+import stage_gpu as sgpu        # noqa: E402  (needs torch)
+from stage_gpu import DEV       # noqa: E402
+
 G_, W_ = 2, 16
 SIZES = (512, 1024, 2048, 4096)
 MERGE_GAPS, MIN_WIDTHS, MAX_SEGMENTS = (0, 1, 3, 40), (1, 2, 5), (1, 16, 256)
 
 
-def _cfg(n, window, k, bands=None):
-    c = cs.cfg_energy_scaled(n) if bands is None else cs.cfg_welch(n, k, bands)
-    c.window = window
-    c.hop = n // 2 if window == cs.WINDOW_HANN else n
-    c.frames_per_epoch = k
-    return c
-
-
-def _zeros(shape, dtype):
-    return torch.zeros(shape, dtype=dtype, device=DEV)
-
-
-def _cfar(s, cfg, iq_t, E, outs=None, spectrum=True):
-    """One CFAR launch over E epochs; returns the device tensors (mask [E][N / 32] int32, spectrum [E][N])."""
-    N, nb = cfg.fft_len, cfg.n_bands
-    if outs is None:
-        outs = {"features": _zeros((E, nb), torch.float32), "decision": _zeros((E,), torch.int32), "occupancy": _zeros((E, nb), torch.uint8),
-                "spectrum": _zeros((E, N), torch.float32) if spectrum else None, "mask": _zeros((E, N // 32), torch.int32)}
-    o = {"features": outs["features"].data_ptr(), "ann_out": 0, "decision": outs["decision"].data_ptr(),
-         "occupancy": outs["occupancy"].data_ptr(), "spectrum": outs["spectrum"].data_ptr() if spectrum else 0}
-    s.run_device_cfar(iq_t.data_ptr(), E, N, o, mask_ptr=outs["mask"].data_ptr())
-    return outs
+def _cfar(s, cfg, iq_t, E, outs=None):
+    """One CFAR launch over E epochs without band_bins; returns the device tensors (mask [E][N / 32] int32, spectrum [E][N])."""
+    return sgpu.cfar_launch(s, cfg, iq_t, E, outs=outs, band_bins=False)
 
 
 class _Out:
@@ -94,7 +77,7 @@ ALL_COMBOS = [(g, mw, ms) for g in MERGE_GAPS for mw in MIN_WIDTHS for ms in MAX
 def test_kernel_matches_twin_on_cfar_output(built, n, window, k):
     """tests/signals.make_epochs traffic through a CA-CFAR launch; the twin reads the mask and the rows that launch wrote."""
     import signals
-    cfg = _cfg(n, window, k)
+    cfg = sgpu.cfg(n, window, k)
     E = 10
     iq, _ = signals.make_epochs(cfg, E, seed=n * 13 + window * 5 + k)
     s = cs.Sensor(cfg)
@@ -109,10 +92,10 @@ def test_kernel_matches_twin_on_cfar_output(built, n, window, k):
                                         (4096, cs.WINDOW_RECT, 10)])
 def test_kernel_matches_twin_on_generated_carriers(built, n, window, k, kind):
     """The device generator's off-grid RRC-QPSK / OFDM carriers: wide segments, many lanes per segment."""
-    cfg = _cfg(n, window, k)
+    cfg = sgpu.cfg(n, window, k)
     E = 10
     spe = cs.samples_per_epoch(cfg)
-    iq_t = _zeros((cs.samples_needed(cfg, E) * 2,), torch.float32)
+    iq_t = sgpu.zeros((cs.samples_needed(cfg, E) * 2,), torch.float32)
     sc = cs.SynthCfg()
     sc.seed, sc.noise_power, sc.signal_rms = 11 + n + kind, 1e-6, 0.02
     sc.tones_per_band, sc.pu_model, sc.signal_kind, sc.n_streams = 8, cs.PU_UNIFORM, kind, 1
@@ -146,14 +129,14 @@ def hand_made(n):
 @pytest.mark.parametrize("n", SIZES)
 def test_hand_made_masks(built, n):
     rng = np.random.default_rng(n)
-    s = cs.Sensor(_cfg(n, cs.WINDOW_RECT, 10))
+    s = cs.Sensor(sgpu.cfg(n, cs.WINDOW_RECT, 10))
     for name, bits, g, mw, ms in hand_made(n):
         det = np.zeros((3, n), bool)
         det[:, list(bits)] = True
         P = rng.gamma(10.0, 1e-4, (3, n)).astype(np.float32)
         P[1] = 1.0                      # every comparison of the peak is a tie: the smallest offset wins
         P[2] = np.repeat(P[2, ::2], 2)                  # equal neighbours
-        _check(s, torch.from_numpy(sg.pack_mask(det).view(np.int32)).to(DEV), torch.from_numpy(P).to(DEV), n, [(g, mw, ms)], f"N={n} {name}")
+        _check(s, sgpu.upload_mask(det), sgpu.upload_rows(P), n, [(g, mw, ms)], f"N={n} {name}")
     s.close()
 
 
@@ -164,9 +147,9 @@ def test_random_masks(built, n, density):
     E = 12
     det = rng.random((E, n)) < density
     P = (rng.gamma(10.0, 1e-4, (E, n)) * np.where(rng.random((E, n)) < 0.02, 1e4, 1.0)).astype(np.float32)
-    s = cs.Sensor(_cfg(n, cs.WINDOW_RECT, 10))
+    s = cs.Sensor(sgpu.cfg(n, cs.WINDOW_RECT, 10))
     combos = [(0, 1, 16), (1, 2, 256), (3, 1, 256), (40, 5, 16), (0, 1, 1), (3, 5, 1), (n - 1, 1, 16), (1, 1, 16), (40, 2, 256)]
-    _check(s, torch.from_numpy(sg.pack_mask(det).view(np.int32)).to(DEV), torch.from_numpy(P).to(DEV), n, combos, f"N={n} density {density}")
+    _check(s, sgpu.upload_mask(det), sgpu.upload_rows(P), n, combos, f"N={n} density {density}")
     s.close()
 
 
@@ -178,8 +161,8 @@ def test_cut_independence_and_headers_only(built, n):
     det[5] = False
     det[6] = True
     P = rng.gamma(10.0, 1e-4, (E, n)).astype(np.float32)
-    mask_t, spec_t = torch.from_numpy(sg.pack_mask(det).view(np.int32)).to(DEV), torch.from_numpy(P).to(DEV)
-    s = cs.Sensor(_cfg(n, cs.WINDOW_RECT, 10))
+    mask_t, spec_t = sgpu.upload_mask(det), sgpu.upload_rows(P)
+    s = cs.Sensor(sgpu.cfg(n, cs.WINDOW_RECT, 10))
     for g, mw, ms in ((0, 1, 16), (3, 2, 4), (40, 1, 256)):
         whole = _segments(s, mask_t, spec_t, E, g, mw, ms)
         parts = _segments(s, mask_t, spec_t, E, g, mw, ms, first=0, count=a)
@@ -206,7 +189,7 @@ def test_refusals_and_any_handle(built):
     det = np.zeros((2, n), bool)
     det[0, [n - 1, 0, 40, 41]] = True
     P = np.random.default_rng(0).gamma(10.0, 1e-4, (2, n)).astype(np.float32)
-    mask_t, spec_t = torch.from_numpy(sg.pack_mask(det).view(np.int32)).to(DEV), torch.from_numpy(P).to(DEV)
+    mask_t, spec_t = sgpu.upload_mask(det), sgpu.upload_rows(P)
     _check(s, mask_t, spec_t, n, [(0, 1, 16)], "REF_MAG handle, uploaded mask")
     out = _Out(2, 16)
 
@@ -243,7 +226,7 @@ def test_end_to_end_pair_across_the_wrap(built, n):
     width 2, n_detected 2, and the last one stored.  An epoch whose mask has bin N - 2 or bin 1 set (a false alarm beside the pair) is
     left out; at most 4 of the 40 may be."""
     k, E = 10, 40
-    cfg = _cfg(n, cs.WINDOW_RECT, k)
+    cfg = sgpu.cfg(n, cs.WINDOW_RECT, k)
     s = cs.Sensor(cfg)
     s.set_cfar(G_, W_, cs.cfar_alpha(1e-3, k, W_), 1)
     outs = _cfar(s, cfg, torch.from_numpy(_wrap_pair(n, k, E, seed=n)).to(DEV), E)
@@ -265,10 +248,8 @@ def test_noise_only_segment_load(built):
     """Recorded, not asserted beyond the twin's agreement: on noise only (N = 4096, K = 10, Pfa 1e-3) the mean n_found per epoch at
     min_width 1 and 2, i.e. how much of the false-alarm load a two-bin minimum removes."""
     n, k, E = 4096, 10, 512
-    cfg = _cfg(n, cs.WINDOW_RECT, k)
-    gen = torch.Generator(device=DEV)
-    gen.manual_seed(77)
-    iq_t = torch.randn(E * k * n * 2, generator=gen, device=DEV, dtype=torch.float32)
+    cfg = sgpu.cfg(n, cs.WINDOW_RECT, k)
+    iq_t = sgpu.noise_batch(E, k, n, seed=77)
     s = cs.Sensor(cfg)
     s.set_cfar(G_, W_, cs.cfar_alpha(1e-3, k, W_), 1)
     outs = _cfar(s, cfg, iq_t, E)
@@ -286,25 +267,14 @@ SPEED_RATIO = 1.158                      # 1.0915 x 1.15 / 1.084
 
 
 def test_cost_next_to_the_cfar_launch(built):
-    """N = 4096, K = 10, rect, 64 bands, the 2.18 GB batch; the method of tests/test_cfar_gpu.py's speed test: each timed window holds
-    R launches issued back to back behind one already queued, the arms alternate, 5 windows each after a warm-up, the best counts.
+    """N = 4096, K = 10, rect, 64 bands, the 2.18 GB batch; the method of tests/stage_gpu.py (best_of_windows): each timed window holds
+    8 launches issued back to back behind one already queued, the arms alternate, 5 windows each after a warm-up, the best counts.
     Arm A is the CFAR launch alone, arm B the same launch followed by crn_segments_device (max_segments 16) on the same stream.  The
     uploaded all-zero, alternating and solid masks and the kernel alone are measured the same way and printed."""
     n, k = 4096, 10
-    cfg = _cfg(n, cs.WINDOW_RECT, k, bands=64)
+    cfg = sgpu.cfg(n, cs.WINDOW_RECT, k, bands=64)
     E = 6656                                  # 6656 x 10 x 4096 x 8 B = 2.18 GB
-    gen = torch.Generator(device=DEV)
-    gen.manual_seed(5)
-    iq_t = torch.randn(E * k * n * 2, generator=gen, device=DEV, dtype=torch.float32)
-    # real traffic: one of the three channels of the energy plan driven in two epochs of three (8 tones, 0.02 rms over the unit noise
-    # would vanish: scaled to the generator's noise power 1), so that epochs carry segments as well as false alarms
-    t = torch.arange(n, device=DEV, dtype=torch.float32)
-    frames = iq_t.view(E, k, n, 2)
-    for j, b in enumerate((300, 301, 302, 303, 1600, 1601, 1602, 3000)):
-        ph = 2 * np.pi * ((b * t) % n) / n
-        sel = slice(j % 3, E, 3)
-        frames[sel, :, :, 0] += 0.3 * torch.cos(ph)
-        frames[sel, :, :, 1] += 0.3 * torch.sin(ph)
+    iq_t = sgpu.add_tones(sgpu.noise_batch(E, k, n), E, k, n)      # real traffic: epochs carry segments as well as false alarms
     s = cs.Sensor(cfg)
     s.set_cfar(G_, W_, cs.cfar_alpha(1e-3, k, W_), 1)
     outs = _cfar(s, cfg, iq_t, E)
@@ -312,17 +282,6 @@ def test_cost_next_to_the_cfar_launch(built):
     words = {"all-zero": 0, "alternating": 0x55555555, "solid": 0xFFFFFFFF}
     masks = {name: torch.full((E, n // 32), w - (1 << 32) if w >> 31 else w, dtype=torch.int32, device=DEV) for name, w in words.items()}
     torch.cuda.synchronize()
-    R = 8
-
-    def timed(fn):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        fn()
-        a.record()
-        for _ in range(R):
-            fn()
-        b.record()
-        b.synchronize()
-        return a.elapsed_time(b) / R
 
     def arm_a():
         _cfar(s, cfg, iq_t, E, outs=outs)
@@ -337,20 +296,12 @@ def test_cost_next_to_the_cfar_launch(built):
     for name, m in masks.items():
         arms["B " + name] = (lambda m=m: arm_b(m))
         arms["alone " + name] = (lambda m=m: alone(m))
-    for fn in arms.values():
-        fn()
-    torch.cuda.synchronize()
-    times = {name: [] for name in arms}
-    for _ in range(5):
-        for name, fn in arms.items():
-            times[name].append(timed(fn))
+    times = sgpu.best_of_windows(arms)
     got_e = out.host()[0]
     arm_b()
     real_e = out.host()[0]
     s.close()
     best = {name: min(v) for name, v in times.items()}
-    for name, v in times.items():
-        print(f"ms per launch, {name}:", " ".join(f"{x:.4f}" for x in v))
     nbytes = E * k * n * 8
     moved = E * (n * 4 + n // 8 + 16 + 16 * 32)
     print(f"N=4096 K=10 rect 64 bands, {E} epochs ({nbytes / 1e9:.2f} GB), spectrum written: arm A (CFAR launch alone) {best['A']:.4f} ms "

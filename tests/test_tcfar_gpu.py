@@ -16,47 +16,20 @@ import tcfar_f64 as tf
 pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
-DEV = "cuda"
+import stage_gpu as sgpu        # noqa: E402  (needs torch)
+from stage_gpu import DEV       # noqa: E402
+
 G_, W_ = 2, 16
-PAD = 256                      # bytes of 0xFF kept behind every array the stage writes
 SIZES = (512, 1024, 2048, 4096)
 WINDOWS = ((2, 0), (4, 2), (64, 1), (128, 16))      # (cells, guard_epochs)
 
 
-def _cfg(n, k=10, bands=None):
-    c = cs.cfg_energy_scaled(n) if bands is None else cs.cfg_welch(n, k, bands)
-    c.window = cs.WINDOW_RECT
-    c.hop = n
-    c.frames_per_epoch = k
-    return c
-
-
-def _upload(P):
-    return torch.from_numpy(np.ascontiguousarray(P, np.float32)).to(DEV)
-
-
-class _Buf:
-    """Named byte arrays on the device, each with PAD bytes behind it, all 0xFF at first."""
-
-    def __init__(self, **sizes):
-        self.sizes = sizes
-        for name, nb in sizes.items():
-            setattr(self, name, torch.full((nb + PAD,), 255, dtype=torch.uint8, device=DEV))
-
-    def host(self):
-        torch.cuda.synchronize()
-        raw = {name: getattr(self, name).cpu().numpy() for name in self.sizes}
-        self.pads_ok = all((raw[name][nb:] == 255).all() for name, nb in self.sizes.items())
-        self.raw = {name: raw[name][:nb] for name, nb in self.sizes.items()}
-        return self.raw
-
-
 def _out(E, n):
-    return _Buf(mask=E * n // 8, rows=E * 16)
+    return sgpu.Padded(mask=E * n // 8, rows=E * 16)
 
 
 def _state(S, n, cells, guard):
-    return _Buf(hist=S * (cells + guard) * n * 4, seen=S * 8)
+    return sgpu.Padded(hist=S * (cells + guard) * n * 4, seen=S * 8)
 
 
 def _launch(s, spec_t, E, q, out, st, or_ptr=0, mask=True, rows=True):
@@ -65,10 +38,9 @@ def _launch(s, spec_t, E, q, out, st, or_ptr=0, mask=True, rows=True):
 
 
 def _views(out, st, E, n, S, H):
-    o, t = out.host(), st.host()
-    assert out.pads_ok and st.pads_ok, "memory behind an array was written"
-    return (np.frombuffer(o["mask"].tobytes(), np.uint32).reshape(E, n // 32), np.frombuffer(o["rows"].tobytes(), np.dtype(cs.TCFAR_ROW_DTYPE)),
-            np.frombuffer(t["hist"].tobytes(), np.uint32).reshape(S, H, n), np.frombuffer(t["seen"].tobytes(), np.int64))
+    out.host(), st.host()
+    assert out.pads_untouched() and st.pads_untouched(), "memory behind an array was written"
+    return (out.view("mask", np.uint32, (E, n // 32)), out.view("rows", cs.TCFAR_ROW_DTYPE), st.view("hist", np.uint32, (S, H, n)), st.view("seen", np.int64))
 
 
 def _nan_state(S, n, cells, guard):
@@ -91,8 +63,8 @@ def _check(s, P, T, cells, guard, rank, alpha, what, or_mask=None):
     E, n = P.shape
     S = E // T
     ranks = [rank] if isinstance(rank, int) else list(rank)
-    spec_t = _upload(P)
-    or_t = None if or_mask is None else torch.from_numpy(tf.pack_mask(or_mask).view(np.int32)).to(DEV)
+    spec_t = sgpu.upload_rows(P)
+    or_t = None if or_mask is None else sgpu.upload_mask(or_mask)
     hist, seen = _nan_state(S, n, cells, guard)
     want = tf.run_ranks(P, T, cells, guard, ranks, alpha, hist, seen, True, or_mask)
     for r in ranks:
@@ -111,7 +83,7 @@ def test_shapes_against_twin(built, n, cells, guard):
     decision, 2 H + 3 has decisions whose cells all lie in the batch, and at 128 + 16 it takes more than one run of a stream."""
     H = cells + guard
     ranks = sorted({1, max(1, cells // 4), cells})
-    s = cs.Sensor(_cfg(n))
+    s = cs.Sensor(sgpu.cfg(n))
     detected = 0
     for T, S, rks, quantised in ((1, 3, ranks[:1], False), (H - 1, 1, ranks[1:2], False), (H, 1, ranks[-1:], True), (H + 1, 3, ranks, False),
                                  (H + 1, 3, ranks[1:2], True), (2 * H + 3, 1, ranks[1:2], False), (2 * H + 3, 1, ranks, True)):
@@ -132,7 +104,7 @@ def test_carry_across_cuts(built, n, cells, guard):
     T = 2 * H + 3
     rank, alpha = max(1, cells // 4), 2.0
     P = tc.gamma_rows(n + cells, S * T, n, quantised=True).reshape(S, T, n)
-    s = cs.Sensor(_cfg(n))
+    s = cs.Sensor(sgpu.cfg(n))
     whole = _check(s, P.reshape(S * T, n), T, cells, guard, rank, alpha, "whole")
     edges = [0, 1, 3, H + 2, T]
     st = _state(S, n, cells, guard)
@@ -140,7 +112,7 @@ def test_carry_across_cuts(built, n, cells, guard):
     for i, (a, b) in enumerate(zip(edges[:-1], edges[1:])):
         E = S * (b - a)
         out = _out(E, n)
-        _launch(s, _upload(P[:, a:b].reshape(E, n)), E, cs.tcfar_params(b - a, cells, rank, alpha, guard, first=i == 0), out, st)
+        _launch(s, sgpu.upload_rows(P[:, a:b].reshape(E, n)), E, cs.tcfar_params(b - a, cells, rank, alpha, guard, first=i == 0), out, st)
         got = _views(out, st, E, n, S, H)
         masks[:, a:b], rows[:, a:b] = got[0].reshape(S, b - a, -1), got[1].reshape(S, b - a)
         assert (got[3] == b).all()
@@ -158,12 +130,12 @@ def test_optional_arguments(built, n):
     H = cells + guard
     T = H + 6
     P = tc.gamma_rows(n + 1, S * T, n)
-    spec_t = _upload(P)
+    spec_t = sgpu.upload_rows(P)
     E = S * T
     rng = np.random.default_rng(n)
     om = rng.random((E, n)) < 0.01
     om[:, [0, 31, 32, 63, 64, n - 1]] = True
-    s = cs.Sensor(_cfg(n))
+    s = cs.Sensor(sgpu.cfg(n))
     q = cs.tcfar_params(T, cells, rank, alpha, guard, first=True)
     plain = _check(s, P, T, cells, guard, rank, alpha, "no d_or_mask")
     with_or = _check(s, P, T, cells, guard, rank, alpha, "d_or_mask given", or_mask=om)
@@ -186,12 +158,12 @@ def test_optional_arguments(built, n):
     cut = H + 2
     P3 = P.reshape(S, T, n)
     out, st = _out(E, n), _state(S, n, cells, guard)
-    _launch(s, _upload(P3[:, :cut].reshape(S * cut, n)), S * cut, cs.tcfar_params(cut, cells, rank, alpha, guard, first=True), out, st, mask=False, rows=False)
+    _launch(s, sgpu.upload_rows(P3[:, :cut].reshape(S * cut, n)), S * cut, cs.tcfar_params(cut, cells, rank, alpha, guard, first=True), out, st, mask=False, rows=False)
     fed = _views(out, st, E, n, S, H)
     assert (out.raw["mask"] == 255).all() and (out.raw["rows"] == 255).all() and (fed[3] == cut).all()
     rest = T - cut
     out = _out(S * rest, n)
-    _launch(s, _upload(P3[:, cut:].reshape(S * rest, n)), S * rest, cs.tcfar_params(rest, cells, rank, alpha, guard), out, st)
+    _launch(s, sgpu.upload_rows(P3[:, cut:].reshape(S * rest, n)), S * rest, cs.tcfar_params(rest, cells, rank, alpha, guard), out, st)
     got = _views(out, st, S * rest, n, S, H)
     assert got[0].tobytes() == plain[0].reshape(S, T, -1)[:, cut:].tobytes() and got[1].tobytes() == plain[1].reshape(S, T)[:, cut:].tobytes()
     assert got[2].tobytes() == plain[2].tobytes() and (got[3] == T).all()
@@ -209,8 +181,8 @@ def test_refusals_with_a_live_handle(built):
     n, T, S = 512, 6, 2
     E = S * T
     L = cs.lib()
-    s = cs.Sensor(_cfg(n))
-    spec_t = _upload(tc.gamma_rows(1, E, n))
+    s = cs.Sensor(sgpu.cfg(n))
+    spec_t = sgpu.upload_rows(tc.gamma_rows(1, E, n))
     out, st = _out(E, n), _state(S, n, 4, 1)
     or_t = torch.zeros((E * n // 32,), dtype=torch.int32, device=DEV)
     inf, nan = float("inf"), float("nan")
@@ -238,7 +210,7 @@ def test_refusals_with_a_live_handle(built):
     assert rc(n_e=0) == 0 and rc(n_e=0, first=False) == 0
     torch.cuda.synchronize()
     after = {**out.host(), **st.host()}
-    assert all((after[k] == before[k]).all() for k in before) and out.pads_ok and st.pads_ok
+    assert all((after[k] == before[k]).all() for k in before) and out.pads_untouched() and st.pads_untouched()
     assert rc(orp=0) == 0 and rc(m=0, r=0) == 0 and rc(m=0) == 0 and rc(r=0) == 0 and rc(epochs_per_stream=E) == 0
     torch.cuda.synchronize()
     s.close()
@@ -259,7 +231,7 @@ def test_end_to_end_shaped_floor_spur_and_dc_spike(built):
     the epochs; LAD sets over 0.2 of the idle bins of the same rows.  Every row equals the twin."""
     n, k, T = E2E["n"], E2E["k"], E2E["eps"]
     H = tc.CELLS + tc.GUARD
-    cfg = _cfg(n, k)
+    cfg = sgpu.cfg(n, k=k)
     iq_t = torch.zeros((cs.samples_needed(cfg, T) * 2,), dtype=torch.float32, device=DEV)
     truth_t = torch.full((T,), -1, dtype=torch.int32, device=DEV)
     sc = cs.SynthCfg()
@@ -268,13 +240,7 @@ def test_end_to_end_shaped_floor_spur_and_dc_spike(built):
     s = cs.Sensor(cfg)
     s.synth_fill_device_ex(iq_t.data_ptr(), T, cs.samples_per_epoch(cfg), sc, truth_ptr=truth_t.data_ptr())
     s.set_cfar(G_, W_, cs.cfar_alpha(1e-3, k, W_), 1)
-    nb = cfg.n_bands
-    z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=DEV)      # noqa: E731
-    outs = {"features": z((T, nb), torch.float32), "decision": z((T,), torch.int32), "occupancy": z((T, nb), torch.uint8),
-            "spectrum": z((T, n), torch.float32), "mask": z((T, n // 32), torch.int32)}
-    s.run_device_cfar(iq_t.data_ptr(), T, n, {"features": outs["features"].data_ptr(), "ann_out": 0, "decision": outs["decision"].data_ptr(),
-                                              "occupancy": outs["occupancy"].data_ptr(), "spectrum": outs["spectrum"].data_ptr()},
-                      mask_ptr=outs["mask"].data_ptr())
+    outs = sgpu.cfar_launch(s, cfg, iq_t, T, band_bins=False)
     outs["spectrum"] *= torch.from_numpy(tc.gain(n).astype(np.float32)).to(DEV)[None, :]
     t_cme = cs.lad_factor(1e-2, k)
     lad_mask = torch.zeros((T, n // 32), dtype=torch.int32, device=DEV)
@@ -324,7 +290,7 @@ SPEED_RATIO = {1: 1.627, 64: 1.750}
 
 @pytest.mark.parametrize("S", [1, 64])
 def test_cost_next_to_the_cfar_launch(built, S):
-    """N = 4096, K = 10, rect, 64 bands, 6656 epochs as one stream and as 64 streams of 104; the method of tests/test_lad_gpu.py's cost test:
+    """N = 4096, K = 10, rect, 64 bands, 6656 epochs as one stream and as 64 streams of 104; the method of tests/stage_gpu.py (best_of_windows):
     each timed window holds 8 launches issued back to back behind one already queued, the arms alternate, 5 windows each after a warm-up,
     the best counts.  Arm A is the CFAR launch alone, arm B the same launch followed by crn_tcfar_device on the same stream with all
     outputs, d_or_mask the CFAR mask, D = 64, guard 1, rank 16, first = 0 (the rows before the batch come from the history, which every
@@ -332,44 +298,19 @@ def test_cost_next_to_the_cfar_launch(built, S):
     n, k = 4096, 10
     cells, guard, rank = tc.CELLS, tc.GUARD, tc.RANK
     H = cells + guard
-    cfg = _cfg(n, k, bands=64)
+    cfg = sgpu.cfg(n, k=k, bands=64)
     E = 6656                                  # 6656 x 10 x 4096 x 8 B = 2.18 GB
     T = E // S
-    gen = torch.Generator(device=DEV)
-    gen.manual_seed(5)
-    iq_t = torch.randn(E * k * n * 2, generator=gen, device=DEV, dtype=torch.float32)
-    # the traffic of the segments cost test: tones over unit noise in two epochs of three
-    t = torch.arange(n, device=DEV, dtype=torch.float32)
-    frames = iq_t.view(E, k, n, 2)
-    for j, b in enumerate((300, 301, 302, 303, 1600, 1601, 1602, 3000)):
-        ph = 2 * np.pi * ((b * t) % n) / n
-        sel = slice(j % 3, E, 3)
-        frames[sel, :, :, 0] += 0.3 * torch.cos(ph)
-        frames[sel, :, :, 1] += 0.3 * torch.sin(ph)
+    # the traffic of every cost test here: tones over unit noise in two epochs of three
+    iq_t = sgpu.add_tones(sgpu.noise_batch(E, k, n), E, k, n)
     s = cs.Sensor(cfg)
     s.set_cfar(G_, W_, cs.cfar_alpha(1e-3, k, W_), 1)
-    nb = cfg.n_bands
-    z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=DEV)      # noqa: E731
-    outs = {"features": z((E, nb), torch.float32), "decision": z((E,), torch.int32), "occupancy": z((E, nb), torch.uint8),
-            "spectrum": z((E, n), torch.float32), "mask": z((E, n // 32), torch.int32), "band_bins": z((E, nb), torch.int32)}
-    o = {"features": outs["features"].data_ptr(), "ann_out": 0, "decision": outs["decision"].data_ptr(), "occupancy": outs["occupancy"].data_ptr(),
-         "spectrum": outs["spectrum"].data_ptr()}
+    outs = sgpu.cfar_outs(cfg, E)
     alpha = cs.tcfar_alpha(1e-3, k, cells, rank)
     out, st = _out(E, n), _state(S, n, cells, guard)
-    R = 8
-
-    def timed(fn):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        fn()
-        a.record()
-        for _ in range(R):
-            fn()
-        b.record()
-        b.synchronize()
-        return a.elapsed_time(b) / R
 
     def arm_a():
-        s.run_device_cfar(iq_t.data_ptr(), E, n, o, mask_ptr=outs["mask"].data_ptr(), band_bins_ptr=outs["band_bins"].data_ptr())
+        sgpu.cfar_launch(s, cfg, iq_t, E, outs=outs)
 
     def stage(first=False):
         _launch(s, outs["spectrum"], E, cs.tcfar_params(T, cells, rank, alpha, guard, first=first), out, st, or_ptr=outs["mask"].data_ptr())
@@ -380,13 +321,7 @@ def test_cost_next_to_the_cfar_launch(built, S):
     arms = {"A": arm_a, "B": arm_b, "alone": stage}
     arm_a()
     stage(first=True)
-    for fn in arms.values():
-        fn()
-    torch.cuda.synchronize()
-    times = {name: [] for name in arms}
-    for _ in range(5):
-        for name, fn in arms.items():
-            times[name].append(timed(fn))
+    times = sgpu.best_of_windows(arms)
     got = _views(out, st, E, n, S, H)
     # the stage computed what the definition says: every 16th epoch of every stream, restated on the kernel's own inputs.  Every call saw
     # the same batch, so the rows before it are the batch's own last H
@@ -405,8 +340,6 @@ def test_cost_next_to_the_cfar_launch(built, S):
         assert (rows["n_new"] == (det & ~tf.unpack_mask(cfar[si, pick], n)).sum(axis=1)).all()
         assert got[2][si].tobytes() == P[si, T - H + ((np.arange(H) - (got[3][si] - H)) % H)].view(np.uint32).tobytes()
     best = {name: min(v) for name, v in times.items()}
-    for name, v in times.items():
-        print(f"ms per launch, {name}:", " ".join(f"{x:.4f}" for x in v))
     nbytes = E * k * n * 8
     print(f"N=4096 K=10 rect 64 bands, {E} epochs ({nbytes / 1e9:.2f} GB) as {S} stream(s), spectrum written: arm A (CFAR launch alone) {best['A']:.4f} ms "
           f"({nbytes / best['A'] / 1e6:.0f} GB/s of input); B / A = {best['B'] / best['A']:.4f}; crn_tcfar_device alone {best['alone'] * 1e3:.1f} us; "

@@ -10,18 +10,23 @@ import numpy as np
 import pytest
 
 import crnsense as cs
-import segments_f64 as sg
 import tracks_carry_f64 as tc
 import tracks_f64 as tk
-from test_tracks_carry_host import collect_calls, hand_made
-from test_tracks_gpu import SOME, _Segs, _Tracks, _cfar, _cfg, _tracks, G_, W_
-from test_tracks_host import E2E, check_end_to_end, e2e_cfg, e2e_synth, runs_of_truth
+from tracks_cases import E2E, carry_hand_made, check_end_to_end, collect_calls, e2e_cfg, e2e_synth, runs_of_truth
 
 pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
-DEV = "cuda"
-COMBOS = SOME + [(1, 15, 2, 64)]          # (slack_bins, max_miss, min_epochs, max_tracks): test_tracks_gpu.py's, and the longest tail
+import stage_gpu as sgpu        # noqa: E402  (needs torch)
+from stage_gpu import DEV       # noqa: E402
+import tracks_gpu_util as tu    # noqa: E402
+
+G_, W_ = 2, 16
+COMBOS = tu.SOME + [(1, 15, 2, 64)]          # (slack_bins, max_miss, min_epochs, max_tracks): test_tracks_gpu.py's, and the longest tail
+
+
+def _cfar(s, cfg, iq_t, E, outs=None):
+    return sgpu.cfar_launch(s, cfg, iq_t, E, outs=outs, band_bins=False)
 
 
 def _pattern(kind, T):
@@ -110,14 +115,14 @@ ALL_CUTS = ("ones", "mixed", "whole")
 @pytest.mark.parametrize("n", [512, 4096])
 def test_kernel_matches_twin_on_make_epochs_traffic(built, n, n_streams):
     import signals
-    cfg = _cfg(n)
+    cfg = sgpu.cfg(n)
     E = 48
     iq, _ = signals.make_epochs(cfg, E, seed=n + 3)
     s = cs.Sensor(cfg)
     s.set_cfar(G_, W_, cs.cfar_alpha(1e-2, 10, W_), 1)
     outs = _cfar(s, cfg, torch.from_numpy(iq).to(DEV), E)
-    _check(s, _Segs.from_masks(s, outs["mask"], outs["spectrum"], 3, 1, 16), n, n_streams, COMBOS, ALL_CUTS, f"make_epochs N={n} max_segments=16")
-    _check(s, _Segs.from_masks(s, outs["mask"], outs["spectrum"], 0, 1, 256), n, n_streams, [COMBOS[2], COMBOS[5]], ("mixed",),
+    _check(s, tu.Segs.from_masks(s, outs["mask"], outs["spectrum"], 3, 1, 16), n, n_streams, COMBOS, ALL_CUTS, f"make_epochs N={n} max_segments=16")
+    _check(s, tu.Segs.from_masks(s, outs["mask"], outs["spectrum"], 0, 1, 256), n, n_streams, [COMBOS[2], COMBOS[5]], ("mixed",),
            f"make_epochs N={n} max_segments=256")
     s.close()
 
@@ -127,7 +132,7 @@ def test_kernel_matches_twin_on_make_epochs_traffic(built, n, n_streams):
 @pytest.mark.parametrize("n", [512, 4096])
 def test_kernel_matches_twin_on_generated_traffic(built, n, pu, n_streams):
     """The device generator's traffic models, CFAR -> segments -> tracks in calls."""
-    cfg = _cfg(n)
+    cfg = sgpu.cfg(n)
     E = 96
     iq_t = torch.zeros((cs.samples_needed(cfg, E) * 2,), dtype=torch.float32, device=DEV)
     sc = cs.SynthCfg()
@@ -138,7 +143,7 @@ def test_kernel_matches_twin_on_generated_traffic(built, n, pu, n_streams):
     s.synth_fill_device_ex(iq_t.data_ptr(), E, cs.samples_per_epoch(cfg), sc, truth_ptr=truth_t.data_ptr())
     s.set_cfar(G_, W_, cs.cfar_alpha(1e-3, 10, W_), 1)
     outs = _cfar(s, cfg, iq_t, E)
-    segs = _Segs.from_masks(s, outs["mask"], outs["spectrum"], 3, 1, 16)
+    segs = tu.Segs.from_masks(s, outs["mask"], outs["spectrum"], 3, 1, 16)
     _check(s, segs, n, n_streams, COMBOS[:4] + COMBOS[5:], ALL_CUTS if n_streams == 4 else ("mixed", "whole"), f"generator pu={pu} N={n} streams={n_streams}")
     s.close()
 
@@ -153,8 +158,8 @@ def test_random_masks(built, density, S):
     det = rng.random((2 * T, n)) < density
     det[rng.random(2 * T) < 0.1] = False                      # some empty epochs
     P = (rng.gamma(10.0, 1e-4, (2 * T, n)) * np.where(rng.random((2 * T, n)) < 0.02, 1e4, 1.0)).astype(np.float32)
-    s = cs.Sensor(_cfg(n))
-    segs = _Segs.from_masks(s, torch.from_numpy(sg.pack_mask(det).view(np.int32)).to(DEV), torch.from_numpy(P).to(DEV), 1, 1, S)
+    s = cs.Sensor(sgpu.cfg(n))
+    segs = tu.Segs.from_masks(s, sgpu.upload_mask(det), sgpu.upload_rows(P), 1, 1, S)
     combos = [(0, 0, 1, 64), (2, 1, 2, 1024), (40, 3, 5, 1), (0, 3, 1, 1024)]
     _check(s, segs, n, 2, combos, ALL_CUTS, f"random masks density {density} max_segments={S}")
     s.close()
@@ -162,10 +167,10 @@ def test_random_masks(built, density, S):
 
 @pytest.mark.parametrize("n", [512, 4096])
 def test_hand_made_lists(built, n):
-    s = cs.Sensor(_cfg(n))
-    for name, E, lists, chunks, kw in hand_made(n):
+    s = cs.Sensor(sgpu.cfg(n))
+    for name, E, lists, chunks, kw in carry_hand_made(n):
         ep, segs = tk.make_lists(E, 4, lists)
-        _sequence(s, _Segs.from_host(ep, segs), n, 1, chunks, kw.get("slack_bins", 1), kw.get("max_miss", 0), kw.get("min_epochs", 1), kw.get("max_tracks", 64))
+        _sequence(s, tu.Segs.from_host(ep, segs), n, 1, chunks, kw.get("slack_bins", 1), kw.get("max_miss", 0), kw.get("min_epochs", 1), kw.get("max_tracks", 64))
     s.close()
 
 
@@ -182,8 +187,8 @@ def test_1100_epochs_in_one_call_after_a_carried_call(built):
     rng = np.random.default_rng(77)
     det = _stay_masks(rng, T, n, 0.004, ((40, 3), (300, 2)))
     P = rng.gamma(10.0, 1e-4, (T, n)).astype(np.float32)
-    s = cs.Sensor(_cfg(n))
-    segs = _Segs.from_masks(s, torch.from_numpy(sg.pack_mask(det).view(np.int32)).to(DEV), torch.from_numpy(P).to(DEV), 0, 1, S)
+    s = cs.Sensor(sgpu.cfg(n))
+    segs = tu.Segs.from_masks(s, sgpu.upload_mask(det), sgpu.upload_rows(P), 0, 1, S)
     rec, *_ = _sequence(s, segs, n, 1, [8, 1100], 1, 1, 2, 1024)
     assert max(int(t["last_t"]) - int(t["first_t"]) for t in rec[0]) > 100
     s.close()
@@ -193,9 +198,9 @@ def test_a_solid_segment_over_8_calls_of_128_epochs(built):
     n, E = 512, 1024
     mask_t = torch.full((E, n // 32), -1, dtype=torch.int32, device=DEV)
     spec_t = torch.rand((E, n), dtype=torch.float32, device=DEV) + 0.5
-    s = cs.Sensor(_cfg(n))
+    s = cs.Sensor(sgpu.cfg(n))
     for S in (1, 16):
-        rec, *_ = _sequence(s, _Segs.from_masks(s, mask_t, spec_t, 0, 1, S), n, 1, [128] * 8, 0, 0, 1, 64)
+        rec, *_ = _sequence(s, tu.Segs.from_masks(s, mask_t, spec_t, 0, 1, S), n, 1, [128] * 8, 0, 0, 1, 64)
         assert len(rec[0]) == 1
         t = rec[0][0]
         assert (t["first_t"], t["last_t"], t["n_epochs_hit"], t["n_segments"], t["flags"], t["width_sum"]) == (0, 1023, 1024, 1024, 3, 1024 * n)
@@ -209,14 +214,14 @@ def _staying(s, n, n_streams, T, S, seed=9):
     for k in range(5):                                        # a few emitters that stay, so that tracks cross the cuts
         det[:, 40 + 90 * k: 43 + 90 * k] |= (rng.random(E) < 0.8)[:, None]
     P = rng.gamma(10.0, 1e-4, (E, n)).astype(np.float32)
-    return _Segs.from_masks(s, torch.from_numpy(sg.pack_mask(det).view(np.int32)).to(DEV), torch.from_numpy(P).to(DEV), 1, 1, S)
+    return tu.Segs.from_masks(s, sgpu.upload_mask(det), sgpu.upload_rows(P), 1, 1, S)
 
 
 def test_the_cut_does_not_show(built):
     """The closed records of a [2, 5, 3, ...] cut and of a one-call run are the same set (keyed by the root); every integer field is
     compared on the records without bit 2 (a one-call run has none), n_epochs_hit inside its bounds on the others."""
     n, T, S = 512, 60, 16
-    s = cs.Sensor(_cfg(n))
+    s = cs.Sensor(sgpu.cfg(n))
     segs = _staying(s, n, 1, T, S)
     ints = [f for f in np.dtype(cs.TRACK_DTYPE).names if f not in ("power_sum", "centre", "flags")]
     for slack, miss, mine, mt in ((1, 0, 1, 1024), (2, 2, 1, 1024), (0, 1, 1, 1024)):
@@ -242,13 +247,13 @@ def test_the_cut_does_not_show(built):
 def test_streams_are_independent(built):
     """4 streams give, stream for stream, the bytes of the integer fields that 4 separate sequences give."""
     n, n_streams, T, S = 512, 4, 40, 16
-    s = cs.Sensor(_cfg(n))
+    s = cs.Sensor(sgpu.cfg(n))
     segs = _staying(s, n, n_streams, T, S, seed=10)
     ints = [f for f in np.dtype(cs.TRACK_DTYPE).names if f not in ("power_sum", "centre")]
     chunks = _pattern("mixed", T)
     together = _sequence(s, segs, n, n_streams, chunks, 2, 2, 2, 8)[0]
     for st in range(n_streams):
-        part = _Segs(T, S)
+        part = tu.Segs(T, S)
         part.epochs, part.segments = segs.epochs[st * T:(st + 1) * T], segs.segments[st * T:(st + 1) * T]
         alone = _sequence(s, part, n, 1, chunks, 2, 2, 2, 8)[0][0]
         assert len(alone) == len(together[st]) > 0
@@ -260,9 +265,9 @@ def test_streams_are_independent(built):
 
 def test_a_carry_that_does_not_match_is_taken_as_empty(built):
     n, T, S = 512, 24, 16
-    s = cs.Sensor(_cfg(n))
+    s = cs.Sensor(sgpu.cfg(n))
     segs = _staying(s, n, 2, T, S, seed=11)
-    first, rest = _Segs(2 * 8, S), _Segs(2 * 16, S)
+    first, rest = tu.Segs(2 * 8, S), tu.Segs(2 * 16, S)
     e, g = segs.epochs.view(2, T, 16), segs.segments.view(2, T, S, 32)
     first.epochs, first.segments = e[:, :8].contiguous().view(16, 16), g[:, :8].contiguous().view(16, S, 32)
     rest.epochs, rest.segments = e[:, 8:].contiguous().view(32, 16), g[:, 8:].contiguous().view(32, S, 32)
@@ -297,7 +302,7 @@ def test_refusals_and_n_epochs_zero(built):
     L = cs.lib()
     s = cs.Sensor(cs.cfg_reference())                         # the handle supplies fft_len and the device only
     ep, sgm = tk.make_lists(E, S, {e: [(50, 4)] for e in range(2, 6)})
-    segs = _Segs.from_host(ep, sgm)
+    segs = tu.Segs.from_host(ep, sgm)
     out = _Carry(2, S, 0, 64, 4)
 
     def rc(h=None, ep_=segs.epochs.data_ptr(), sg_=segs.segments.data_ptr(), E_=E, q=None, t0=0, cy=out.carry.data_ptr(), cb=out.carry_bytes,
@@ -336,7 +341,7 @@ def test_refusals_and_n_epochs_zero(built):
 
 
 def test_end_to_end_markov_dwell_runs_in_calls_of_8_epochs(built):
-    """test_tracks_gpu.py's end-to-end case (E2E of tests/test_tracks_host.py: 64 streams x 104 epochs, N = 4096) with the tracks stage fed
+    """test_tracks_gpu.py's end-to-end case (E2E of tests/tracks_cases.py: 64 streams x 104 epochs, N = 4096) with the tracks stage fed
     8 epochs at a time: every dwell run of the truth comes back as exactly one record with the run's first and last global epoch."""
     cfg = e2e_cfg()
     n_streams, eps, step = 64, E2E["eps"], 8
@@ -348,7 +353,7 @@ def test_end_to_end_markov_dwell_runs_in_calls_of_8_epochs(built):
     s.set_cfar(E2E["guard"], E2E["train"], cs.cfar_alpha(E2E["pfa"], E2E["k"], E2E["train"]), 1)
     outs = _cfar(s, cfg, iq_t, E)
     S = E2E["max_segments"]
-    segs = _Segs.from_masks(s, outs["mask"], outs["spectrum"], E2E["merge_gap"], E2E["min_width"], S)
+    segs = tu.Segs.from_masks(s, outs["mask"], outs["spectrum"], E2E["merge_gap"], E2E["min_width"], S)
     ep_d, sg_d = segs.epochs.view(n_streams, eps, 16), segs.segments.view(n_streams, eps, S, 32)
     carry = _Carry(n_streams, S, E2E["max_miss"], E2E["max_tracks"], step)
 
@@ -377,77 +382,53 @@ MARGIN = 1.06
 
 
 def test_cost_next_to_tracks_device(built):
-    """N = 4096, K = 10, rect, 64 bands, 6656 epochs, 16 slots, the traffic of tests/test_tracks_gpu.py's speed test.  Each timed window
-    holds 8 launches issued back to back behind one already queued, the arms alternate, 5 windows each after a warm-up, the best
-    counts.  Arm B's calls follow one another in time (t_start advances by 104 per call), so every call finds the carry the previous one
-    left.  Printed, not asserted: one stream with an emitter that stays in every epoch, cut into 64 calls of 104 epochs, next to
-    crn_tracks_device on the uncut stream of 6656 epochs."""
+    """N = 4096, K = 10, rect, 64 bands, 6656 epochs, 16 slots, the traffic of tests/test_tracks_gpu.py's speed test; the method of
+    tests/stage_gpu.py (best_of_windows): each timed window holds 8 launches issued back to back behind one already queued, the arms
+    alternate, 5 windows each after a warm-up, the best counts.  Arm B's calls follow one another in time (t_start advances by 104 per
+    call), so every call finds the carry the previous one left.  Printed, not asserted: one stream with an emitter that stays in every
+    epoch, cut into 64 calls of 104 epochs, next to crn_tracks_device on the uncut stream of 6656 epochs."""
     n, k = 4096, 10
-    cfg = _cfg(n, k, bands=64)
+    cfg = sgpu.cfg(n, k=k, bands=64)
     E, S, eps = 6656, 16, 104
-    gen = torch.Generator(device=DEV)
-    gen.manual_seed(5)
-    iq_t = torch.randn(E * k * n * 2, generator=gen, device=DEV, dtype=torch.float32)
-    t = torch.arange(n, device=DEV, dtype=torch.float32)
-    frames = iq_t.view(E, k, n, 2)
-    for j, b in enumerate((300, 301, 302, 303, 1600, 1601, 1602, 3000)):
-        ph = 2 * np.pi * ((b * t) % n) / n
-        sel = slice(j % 3, E, 3)
-        frames[sel, :, :, 0] += 0.3 * torch.cos(ph)
-        frames[sel, :, :, 1] += 0.3 * torch.sin(ph)
+    iq_t = sgpu.add_tones(sgpu.noise_batch(E, k, n), E, k, n)
     s = cs.Sensor(cfg)
     s.set_cfar(G_, W_, cs.cfar_alpha(1e-3, k, W_), 1)
     outs = _cfar(s, cfg, iq_t, E)
-    segs = _Segs.from_masks(s, outs["mask"], outs["spectrum"], 0, 1, S)
+    segs = tu.Segs.from_masks(s, outs["mask"], outs["spectrum"], 0, 1, S)
     stay = outs["mask"].clone()
     stay[:, 10] |= 0x70
-    segs_stay = _Segs.from_masks(s, stay, outs["spectrum"], 0, 1, S)
-    out_a, out_1 = _Tracks(E, S, 64, 64), _Tracks(E, S, 1, 64)
+    segs_stay = tu.Segs.from_masks(s, stay, outs["spectrum"], 0, 1, S)
+    out_a, out_1 = tu.Tracks(E, S, 64, 64), tu.Tracks(E, S, 1, 64)
     carry = _Carry(64, S, 0, 64, eps)
     carry_1 = _Carry(1, S, 0, 64, eps)
     torch.cuda.synchronize()
-    R = 8
     clock = {"t": 0}
 
     def arm_a():
-        _tracks(s, segs, eps, 1, 0, 1, 64, out=out_a, labels=False)
+        tu.tracks(s, segs, eps, 1, 0, 1, 64, out=out_a, labels=False)
 
     def arm_b():
         carry.call(s, segs.epochs, segs.segments, eps, clock["t"], 0, 1, 1, sync=False)
         clock["t"] += eps
 
     def uncut_stay():
-        _tracks(s, segs_stay, E, 1, 0, 1, 64, out=out_1, labels=False)
+        tu.tracks(s, segs_stay, E, 1, 0, 1, 64, out=out_1, labels=False)
 
     def cut_stay():
         for c in range(64):
             carry_1.call(s, segs_stay.epochs[c * eps:(c + 1) * eps], segs_stay.segments[c * eps:(c + 1) * eps], eps, c * eps, c == 63, 1, 1, sync=False)
 
-    def timed(fn, reps=R):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        fn()
-        a.record()
-        for _ in range(reps):
-            fn()
-        b.record()
-        b.synchronize()
-        return a.elapsed_time(b) / reps
+    def best_of_3(fn):
+        """ms per call: 3 windows of 2 calls each, behind one already queued"""
+        return min(sgpu.best_of_windows({"stay": fn}, windows=3, launches=2, warm_up=False, report=False)["stay"])
     arms = {"A": arm_a, "B": arm_b}
-    for fn in arms.values():
-        fn()
-    torch.cuda.synchronize()
-    times = {name: [] for name in arms}
-    for _ in range(5):
-        for name, fn in arms.items():
-            times[name].append(timed(fn))
+    times = sgpu.best_of_windows(arms)
     hb = carry.host()[0]
     ha = out_a.host()[0]
-    stay_us = {"uncut": min(timed(uncut_stay, 2) for _ in range(3)) * 1e3, "cut": min(timed(cut_stay, 2) for _ in range(3)) * 1e3}
+    stay_us = {"uncut": best_of_3(uncut_stay) * 1e3, "cut": best_of_3(cut_stay) * 1e3}
     h1, tr1, _ = carry_1.host()
     s.close()
     best = {name: min(v) for name, v in times.items()}
-    for name, v in times.items():
-        print(f"ms per launch, {name}:", " ".join(f"{x:.4f}" for x in v))
     ratio = best["B"] / best["A"]
     print(f"N=4096, {E} epochs in 64 streams x {eps}, {S} slots, {int(ha['n_nodes'].sum())} nodes: crn_tracks_device {best['A'] * 1e3:.1f} us, "
           f"crn_tracks_carry_device with a warm carry {best['B'] * 1e3:.1f} us ({int(hb['n_open'].sum())} tracks open): B / A = {ratio:.4f}")

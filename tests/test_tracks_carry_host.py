@@ -13,7 +13,7 @@ import crnsense as cs
 import segments_f64 as sg
 import tracks_carry_f64 as tc
 import tracks_f64 as tk
-from test_tracks_host import E2E, check_end_to_end, e2e_cfg, e2e_synth, runs_of_truth
+from tracks_cases import E2E, carry_hand_made, check_end_to_end, collect_calls, e2e_cfg, e2e_synth, runs_of_truth
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 N = 256
@@ -199,33 +199,8 @@ def test_a_carry_that_does_not_match_is_taken_as_empty():
     assert h2["status"][0] == 1
 
 
-def hand_made(n):
-    """(name, E, {epoch: [(lo, width[, power, centroid, peak])]}, the calls' lengths, parameters): the lists of the cases above at size n,
-    for tests/test_tracks_carry_gpu.py to upload (4 slots per epoch); the answers are asserted above, there the kernel must equal the twin."""
-    merge = {e: [(10, 2), (20, 2)] for e in (0, 1, 2, 4, 5)}
-    merge[3] = [(10, 12)]
-    wrap = {0: [(1, 1, 3.0, 0.0), (n - 2, 1, 1.0, 0.0)], 1: [(1, 1, 3.0, 0.0), (n - 2, 1, 1.0, 0.0)], 2: [(n - 2, 4, 1.0, 1.5)]}
-    four = {0: [(20 * k, 2) for k in range(4)], 1: [(20 * k, 2) for k in range(4)], 2: [(200, 1)]}
-    return [("one emitter across three calls", 12, {e: [(10, 3, 2.0 + e, 0.5 * e % 3, 1.0 + e)] for e in range(3, 10)}, [4, 4, 4], dict(slack_bins=0)),
-            ("gap on the cut", 8, {e: [(40, 2)] for e in (2, 3, 5, 6)}, [4, 4], dict(slack_bins=0, max_miss=1)),
-            ("gap before the cut", 8, {e: [(40, 2)] for e in (2, 3, 5, 6)}, [5, 3], dict(slack_bins=0, max_miss=1)),
-            ("gap, no miss allowed", 8, {e: [(40, 2)] for e in (2, 3, 5, 6)}, [4, 4], dict(slack_bins=0, max_miss=0)),
-            ("calls of one epoch, max_miss 3", 14, {0: [(7, 2)], 4: [(8, 2)], 8: [(7, 2)]}, [1] * 14, dict(slack_bins=0, max_miss=3)),
-            ("four misses", 14, {0: [(7, 2)], 5: [(8, 2)]}, [1] * 14, dict(slack_bins=0, max_miss=3)),
-            ("two carried carriers merged", 6, merge, [3, 3], dict(slack_bins=0)), ("merged within a call", 6, merge, [4, 2], dict(slack_bins=0)),
-            ("pair across the wrap", 2, {0: [(n - 1, 1, 1.0, 0.0)], 1: [(0, 1, 3.0, 0.0)]}, [1, 1], dict(slack_bins=1)),
-            ("carried tracks joined across the wrap", 3, wrap, [2, 1], dict(slack_bins=0)),
-            ("a single waits", 8, {3: [(100, 2)], 4: [(100, 2)]}, [4, 4], dict(slack_bins=0, min_epochs=2)),
-            ("a false alarm", 8, {3: [(100, 2)]}, [4, 4], dict(slack_bins=0, min_epochs=2)),
-            ("flush", 4, {e: [(50, 4)] for e in range(4)}, [4], dict(slack_bins=0)), ("truncation", 3, four, [3], dict(slack_bins=0, max_tracks=2)),
-            ("truncation of the open list", 6, {e: [(20 * k, 2) for k in range(4)] for e in range(6)}, [2, 2, 2], dict(slack_bins=0, max_tracks=2)),
-            ("width N", 4, {0: [(0, n)], 1: [(77, 1), (200, 3)], 2: [(77, 1)], 3: [(0, n)]}, [1, 2, 1], dict(slack_bins=0)),
-            ("zero power", 3, {e: [(9, 2, 0.0, 0.0, 0.0)] for e in range(3)}, [1, 1, 1], dict(slack_bins=0)),
-            ("nothing at all", 6, {}, [3, 3], dict(slack_bins=1, max_miss=1))]
-
-
 def test_hand_made_lists_run_through_the_twin_and_match_the_whole_batch():
-    for name, E, lists, chunks, kw in hand_made(N):
+    for name, E, lists, chunks, kw in carry_hand_made(N):
         ep, segs = tk.make_lists(E, 4, lists)
         got = tc.closed_records(tc.run_cut(ep, segs, N, chunks, **{**kw, "max_tracks": 64}))
         st, whole, _ = tk.run(ep, segs, N, E, kw.get("slack_bins", 1), kw.get("max_miss", 0), kw.get("min_epochs", 1), 64)
@@ -260,24 +235,6 @@ def test_chain_on_the_twins_in_calls_of_8_epochs(built):
     n_runs, n_other = check_end_to_end(cfg, truth.reshape(n_streams, eps), streams, tracks)
     assert n_runs == sum(len(runs_of_truth(r)) for r in truth.reshape(n_streams, eps))
     print(f"twins, {n_streams} streams x {eps} epochs in calls of {step}: {n_runs} dwell runs each one record, {n_other} other records")
-
-
-def collect_calls(call, n_streams, eps, step, dtype=tk.TRACK_F64):
-    """Runs call(states, t_start, flush) -> (headers, tracks, open, states) over eps epochs in calls of `step` and gathers every
-    stream's closed records into (streams, tracks) as check_end_to_end takes them."""
-    per_stream, states = [[] for _ in range(n_streams)], None
-    for t in range(0, eps, step):
-        h, tr, _, states = call(states, t, int(t + step >= eps))
-        for k in range(n_streams):
-            assert h["n_found"][k] == h["n_stored"][k]
-            per_stream[k] += [tr[k, i] for i in range(int(h["n_stored"][k]))]
-    most = max(1, max(len(r) for r in per_stream))
-    streams, tracks = np.zeros(n_streams, tk.STREAM_F64), np.zeros((n_streams, most), dtype)
-    for k, recs in enumerate(per_stream):
-        streams["n_found"][k] = streams["n_stored"][k] = len(recs)
-        for i, r in enumerate(recs):
-            tracks[k, i] = r
-    return streams, tracks
 
 
 # ---- the C ABI ----------------------------------------------------------------------------------------------------------------

@@ -10,95 +10,22 @@ import numpy as np
 import pytest
 
 import crnsense as cs
-import segments_f64 as sg
 import tracks_f64 as tk
-from test_tracks_host import E2E, check_end_to_end, e2e_cfg, e2e_synth, runs_of_truth
+from tracks_cases import E2E, check_end_to_end, e2e_cfg, e2e_synth, runs_of_truth
 
 pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
-DEV = "cuda"
+import stage_gpu as sgpu        # noqa: E402  (needs torch)
+from stage_gpu import DEV       # noqa: E402
+import tracks_gpu_util as tu    # noqa: E402
+
 G_, W_ = 2, 16
 SLACKS, MAX_MISS, MIN_EPOCHS, MAX_TRACKS, MAX_SEGMENTS = (0, 2, 40), (0, 1, 3), (1, 2, 5), (1, 64, 1024), (1, 16, 256)
 
 
-def _cfg(n, k=10, bands=None):
-    c = cs.cfg_energy_scaled(n) if bands is None else cs.cfg_welch(n, k, bands)
-    c.window, c.hop, c.frames_per_epoch = cs.WINDOW_RECT, n, k
-    return c
-
-
 def _cfar(s, cfg, iq_t, E, outs=None):
-    N, nb = cfg.fft_len, cfg.n_bands
-    if outs is None:
-        z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=DEV)      # noqa: E731
-        outs = {"features": z((E, nb), torch.float32), "decision": z((E,), torch.int32), "occupancy": z((E, nb), torch.uint8),
-                "spectrum": z((E, N), torch.float32), "mask": z((E, N // 32), torch.int32)}
-    o = {"features": outs["features"].data_ptr(), "ann_out": 0, "decision": outs["decision"].data_ptr(),
-         "occupancy": outs["occupancy"].data_ptr(), "spectrum": outs["spectrum"].data_ptr()}
-    s.run_device_cfar(iq_t.data_ptr(), E, N, o, mask_ptr=outs["mask"].data_ptr())
-    return outs
-
-
-class _Segs:
-    """The two arrays crn_segments_device writes, on the device."""
-
-    def __init__(self, E, S):
-        self.E, self.S = E, S
-        self.epochs = torch.full((E, 16), 255, dtype=torch.uint8, device=DEV)
-        self.segments = torch.full((E, S, 32), 255, dtype=torch.uint8, device=DEV)
-
-    @classmethod
-    def from_masks(cls, s, mask_t, spec_t, merge_gap=0, min_width=1, S=16):
-        self = cls(mask_t.shape[0], S)
-        s.segments_device(mask_t.data_ptr(), spec_t.data_ptr(), self.E, self.epochs.data_ptr(), self.segments.data_ptr(),
-                          merge_gap=merge_gap, min_width=min_width, max_segments=S)
-        return self
-
-    @classmethod
-    def from_host(cls, ep, segs):
-        """Upload hand-made lists (tracks_f64.make_lists) in the kernel's layout."""
-        E, S = segs.shape
-        self = cls(E, S)
-        e = np.zeros(E, cs.SEGMENT_EPOCH_DTYPE)
-        e["n_found"], e["n_stored"] = ep["n_found"], ep["n_stored"]
-        g = np.zeros((E, S), cs.SEGMENT_DTYPE)
-        for f in ("lo", "width", "power", "peak_power", "centroid"):
-            g[f] = segs[f]
-        self.epochs = torch.from_numpy(np.frombuffer(e.tobytes(), np.uint8).reshape(E, 16).copy()).to(DEV)
-        self.segments = torch.from_numpy(np.frombuffer(g.tobytes(), np.uint8).reshape(E, S, 32).copy()).to(DEV)
-        return self
-
-    def host(self):
-        torch.cuda.synchronize()
-        return (np.frombuffer(self.epochs.cpu().numpy().tobytes(), cs.SEGMENT_EPOCH_DTYPE),
-                np.frombuffer(self.segments.cpu().numpy().tobytes(), cs.SEGMENT_DTYPE).reshape(self.E, self.S))
-
-
-class _Tracks:
-    def __init__(self, E, S, n_streams, max_tracks, max_miss=0):
-        self.shape = (E, S, n_streams, max_tracks)
-        self.streams = torch.full((n_streams, 16), 255, dtype=torch.uint8, device=DEV)
-        self.tracks = torch.full((n_streams, max_tracks, 64), 255, dtype=torch.uint8, device=DEV)
-        self.track_of = torch.full((E, S, 4), 0x7F, dtype=torch.uint8, device=DEV)
-        self.ws_bytes = cs.tracks_workspace_bytes(E, S, E // n_streams, max_miss, 1, max_tracks)
-        self.ws = torch.full((self.ws_bytes,), 255, dtype=torch.uint8, device=DEV)
-
-    def host(self):
-        E, S, n_streams, mt = self.shape
-        torch.cuda.synchronize()
-        return (np.frombuffer(self.streams.cpu().numpy().tobytes(), cs.TRACK_STREAM_DTYPE),
-                np.frombuffer(self.tracks.cpu().numpy().tobytes(), cs.TRACK_DTYPE).reshape(n_streams, mt),
-                np.frombuffer(self.track_of.cpu().numpy().tobytes(), np.int32).reshape(E, S))
-
-
-def _tracks(s, segs, eps, slack=1, miss=0, mine=1, mt=64, out=None, labels=True):
-    E, S = segs.E, segs.S
-    out = _Tracks(E, S, E // eps, mt, miss) if out is None else out
-    s.tracks_device(segs.epochs.data_ptr(), segs.segments.data_ptr(), E, out.streams.data_ptr(), out.tracks.data_ptr(), out.ws.data_ptr(),
-                    out.ws_bytes, track_of_ptr=out.track_of.data_ptr() if labels else 0, max_segments=S, epochs_per_stream=eps,
-                    slack_bins=slack, max_miss=miss, min_epochs=mine, max_tracks=mt)
-    return out
+    return sgpu.cfar_launch(s, cfg, iq_t, E, outs=outs, band_bins=False)
 
 
 def _check(s, segs, n, eps, combos, what):
@@ -106,7 +33,7 @@ def _check(s, segs, n, eps, combos, what):
     ep, sgm = segs.host()
     roots, worst_p, worst_c, found = {}, 0.0, 0.0, 0
     for slack, miss, mine, mt in combos:
-        got = _tracks(s, segs, eps, slack, miss, mine, mt).host()
+        got = tu.tracks(s, segs, eps, slack, miss, mine, mt).host()
         if (slack, miss) not in roots:
             ns = np.clip(ep["n_stored"].astype(np.int64), 0, segs.S)
             roots[slack, miss] = tk.components(ns, sgm["lo"].astype(np.int64), sgm["width"].astype(np.int64), n, eps, slack, miss)
@@ -117,22 +44,19 @@ def _check(s, segs, n, eps, combos, what):
           f"stream {found}, power_sum error {worst_p:.2e} (bound {tk.POWER_TOL:.2e}), centre error {worst_c:.2e} bins (bound {n * tk.CENTRE_TOL:.2e})")
 
 
-SOME = [(1, 0, 1, 64), (0, 1, 2, 64), (2, 3, 1, 1024), (40, 1, 5, 64), (2, 0, 2, 1)]
-
-
 @pytest.mark.parametrize("n", [512, 4096])
 def test_kernel_matches_twin_on_make_epochs_traffic(built, n):
     import signals
-    cfg = _cfg(n)
+    cfg = sgpu.cfg(n)
     E = 48
     iq, _ = signals.make_epochs(cfg, E, seed=n + 3)
     s = cs.Sensor(cfg)
     s.set_cfar(G_, W_, cs.cfar_alpha(1e-2, 10, W_), 1)
     outs = _cfar(s, cfg, torch.from_numpy(iq).to(DEV), E)
     for S, g in ((16, 3), (256, 0)):
-        segs = _Segs.from_masks(s, outs["mask"], outs["spectrum"], g, 1, S)
+        segs = tu.Segs.from_masks(s, outs["mask"], outs["spectrum"], g, 1, S)
         for eps in (E, E // 4):
-            _check(s, segs, n, eps, SOME, f"make_epochs N={n} max_segments={S} eps={eps}")
+            _check(s, segs, n, eps, tu.SOME, f"make_epochs N={n} max_segments={S} eps={eps}")
     s.close()
 
 
@@ -142,7 +66,7 @@ def test_kernel_matches_twin_on_make_epochs_traffic(built, n):
 @pytest.mark.parametrize("n", [512, 4096])
 def test_kernel_matches_twin_on_generated_traffic(built, n, pu, n_streams, kind):
     """The device generator's traffic models, CFAR -> segments -> tracks."""
-    cfg = _cfg(n)
+    cfg = sgpu.cfg(n)
     E = 256
     spe = cs.samples_per_epoch(cfg)
     iq_t = torch.zeros((cs.samples_needed(cfg, E) * 2,), dtype=torch.float32, device=DEV)
@@ -154,8 +78,8 @@ def test_kernel_matches_twin_on_generated_traffic(built, n, pu, n_streams, kind)
     s.synth_fill_device_ex(iq_t.data_ptr(), E, spe, sc, truth_ptr=truth_t.data_ptr())
     s.set_cfar(G_, W_, cs.cfar_alpha(1e-3, 10, W_), 1)
     outs = _cfar(s, cfg, iq_t, E)
-    segs = _Segs.from_masks(s, outs["mask"], outs["spectrum"], 3 if kind == cs.SIG_RRC_QPSK else 0, 1, 16)
-    _check(s, segs, n, E // n_streams, SOME[:4], f"generator pu={pu} kind={kind} N={n} streams={n_streams}")
+    segs = tu.Segs.from_masks(s, outs["mask"], outs["spectrum"], 3 if kind == cs.SIG_RRC_QPSK else 0, 1, 16)
+    _check(s, segs, n, E // n_streams, tu.SOME[:4], f"generator pu={pu} kind={kind} N={n} streams={n_streams}")
     s.close()
 
 
@@ -168,10 +92,10 @@ def test_parameter_sweep_on_random_masks(built, density):
     det = rng.random((E, n)) < density
     det[rng.random(E) < 0.1] = False                          # some empty epochs
     P = (rng.gamma(10.0, 1e-4, (E, n)) * np.where(rng.random((E, n)) < 0.02, 1e4, 1.0)).astype(np.float32)
-    mask_t, spec_t = torch.from_numpy(sg.pack_mask(det).view(np.int32)).to(DEV), torch.from_numpy(P).to(DEV)
-    s = cs.Sensor(_cfg(n))
+    mask_t, spec_t = sgpu.upload_mask(det), sgpu.upload_rows(P)
+    s = cs.Sensor(sgpu.cfg(n))
     for S in MAX_SEGMENTS:
-        segs = _Segs.from_masks(s, mask_t, spec_t, 1, 1, S)
+        segs = tu.Segs.from_masks(s, mask_t, spec_t, 1, 1, S)
         combos = [(sl, mi, me, mt) for sl in SLACKS for mi in MAX_MISS for me in MIN_EPOCHS for mt in MAX_TRACKS]
         _check(s, segs, n, eps, combos, f"random masks density {density} max_segments={S}")
     s.close()
@@ -200,10 +124,10 @@ def hand_made(n):
 
 @pytest.mark.parametrize("n", [512, 4096])
 def test_hand_made_lists(built, n):
-    s = cs.Sensor(_cfg(n))
+    s = cs.Sensor(sgpu.cfg(n))
     for name, E, eps, lists, combos in hand_made(n):
         ep, segs = tk.make_lists(E, 4, lists)
-        _check(s, _Segs.from_host(ep, segs), n, eps, combos, f"N={n} {name}")
+        _check(s, tu.Segs.from_host(ep, segs), n, eps, combos, f"N={n} {name}")
     s.close()
 
 
@@ -215,12 +139,12 @@ def test_worst_cases_at_4096_epochs(built, case):
     word = 0xFFFFFFFF if case == "solid" else 0x55555555
     mask_t = torch.full((E, n // 32), word - (1 << 32) if word >> 31 else word, dtype=torch.int32, device=DEV)
     spec_t = torch.rand((E, n), dtype=torch.float32, device=DEV) + 0.5
-    s = cs.Sensor(_cfg(n))
+    s = cs.Sensor(sgpu.cfg(n))
     if case == "solid":
         for S in (1, 16):
-            _check(s, _Segs.from_masks(s, mask_t, spec_t, 0, 1, S), n, E, [(0, 0, 1, 64), (40, 3, 5, 1)], f"solid, max_segments {S}")
+            _check(s, tu.Segs.from_masks(s, mask_t, spec_t, 0, 1, S), n, E, [(0, 0, 1, 64), (40, 3, 5, 1)], f"solid, max_segments {S}")
     else:
-        _check(s, _Segs.from_masks(s, mask_t, spec_t, 0, 1, 256), n, E, [(0, 3, 1, 1024), (2, 3, 2, 64)], "alternating")
+        _check(s, tu.Segs.from_masks(s, mask_t, spec_t, 0, 1, 256), n, E, [(0, 3, 1, 1024), (2, 3, 2, 64)], "alternating")
     s.close()
 
 
@@ -229,8 +153,8 @@ def test_refusals_and_n_epochs_zero(built):
     L = cs.lib()
     s = cs.Sensor(cs.cfg_reference())                         # the handle supplies fft_len and the device only
     ep, sgm = tk.make_lists(E, S, {e: [(50, 4)] for e in range(2, 6)})
-    segs = _Segs.from_host(ep, sgm)
-    out = _Tracks(E, S, 2, 64)
+    segs = tu.Segs.from_host(ep, sgm)
+    out = tu.Tracks(E, S, 2, 64)
 
     def rc(h=None, ep_=segs.epochs.data_ptr(), sg_=segs.segments.data_ptr(), E_=E, q=None, st=out.streams.data_ptr(), tr=out.tracks.data_ptr(),
            of=out.track_of.data_ptr(), ws=out.ws.data_ptr(), nb=out.ws_bytes, **kw):
@@ -249,12 +173,12 @@ def test_refusals_and_n_epochs_zero(built):
     assert rc(slack=n - 1) == 0 and rc(miss=15) == 0 and rc(of=0) == 0 and rc(mt=1) == 0 and rc(eps=8) == 0
     _check(s, segs, n, 4, [(0, 0, 1, 64)], "REF_MAG handle")
     # n_epochs = 0 succeeds and launches nothing
-    fresh = _Tracks(E, S, 2, 64)
+    fresh = tu.Tracks(E, S, 2, 64)
     assert rc(E_=0, st=fresh.streams.data_ptr(), tr=fresh.tracks.data_ptr(), of=fresh.track_of.data_ptr()) == 0
     torch.cuda.synchronize()
     assert (fresh.streams.cpu().numpy() == 255).all() and (fresh.tracks.cpu().numpy() == 255).all() and (fresh.track_of.cpu().numpy() == 0x7F).all()
     # d_track_of = NULL leaves the labels alone and changes nothing else
-    a, b = _tracks(s, segs, 4), _tracks(s, segs, 4, labels=False)
+    a, b = tu.tracks(s, segs, 4), tu.tracks(s, segs, 4, labels=False)
     torch.cuda.synchronize()
     assert a.tracks.cpu().numpy().tobytes() == b.tracks.cpu().numpy().tobytes() and (b.track_of.cpu().numpy() == 0x7F).all()
     s.close()
@@ -270,20 +194,20 @@ def test_stream_independence_and_repeatability(built):
     for k in range(6):                                        # a few emitters that stay, so that tracks are long
         det[:, 40 + 70 * k: 43 + 70 * k] |= (rng.random(E) < 0.8)[:, None]
     P = rng.gamma(10.0, 1e-4, (E, n)).astype(np.float32)
-    s = cs.Sensor(_cfg(n))
-    segs = _Segs.from_masks(s, torch.from_numpy(sg.pack_mask(det).view(np.int32)).to(DEV), torch.from_numpy(P).to(DEV), 1, 1, S)
+    s = cs.Sensor(sgpu.cfg(n))
+    segs = tu.Segs.from_masks(s, sgpu.upload_mask(det), sgpu.upload_rows(P), 1, 1, S)
     ints = [f for f in np.dtype(cs.TRACK_DTYPE).names if f not in ("power_sum", "centre")]
     for slack, miss, mine, mt in ((1, 0, 1, 64), (2, 2, 2, 8)):
-        whole = _tracks(s, segs, eps, slack, miss, mine, mt)
-        again = _tracks(s, segs, eps, slack, miss, mine, mt)
+        whole = tu.tracks(s, segs, eps, slack, miss, mine, mt)
+        again = tu.tracks(s, segs, eps, slack, miss, mine, mt)
         w, a = whole.host(), again.host()
         assert w[0].tobytes() == a[0].tobytes() and (w[2] == a[2]).all()
         for f in ints:
             assert w[1][f].tobytes() == a[1][f].tobytes(), f
         for st in range(n_streams):
-            part = _Segs(eps, S)
+            part = tu.Segs(eps, S)
             part.epochs, part.segments = segs.epochs[st * eps:(st + 1) * eps], segs.segments[st * eps:(st + 1) * eps]
-            one = _tracks(s, part, eps, slack, miss, mine, mt).host()
+            one = tu.tracks(s, part, eps, slack, miss, mine, mt).host()
             assert one[0].tobytes() == w[0][st:st + 1].tobytes(), st
             assert one[1].tobytes() == w[1][st:st + 1].tobytes(), st
             assert (one[2] == w[2][st * eps:(st + 1) * eps]).all(), st
@@ -292,7 +216,7 @@ def test_stream_independence_and_repeatability(built):
 
 
 def test_end_to_end_markov_dwell_runs(built):
-    """The parameters chosen on the twins (tests/test_tracks_host.py, E2E): intended-Markov CW traffic from crn_synth_fill_device_ex with
+    """The parameters chosen on the twins (tests/tracks_cases.py, E2E): intended-Markov CW traffic from crn_synth_fill_device_ex with
     d_truth, 64 streams x 104 epochs, N = 4096, max_miss 0, min_epochs 1.  Every maximal run of one band in a stream's truth has exactly
     one track whose centre lies inside that band and whose first_t / last_t are the run's; every other track has n_epochs_hit 1; the
     3 x 3 transition counts rebuilt from the matched tracks equal those counted in the truth."""
@@ -305,8 +229,8 @@ def test_end_to_end_markov_dwell_runs(built):
     s.synth_fill_device_ex(iq_t.data_ptr(), E, cs.samples_per_epoch(cfg), e2e_synth(n_streams), truth_ptr=truth_t.data_ptr())
     s.set_cfar(E2E["guard"], E2E["train"], cs.cfar_alpha(E2E["pfa"], E2E["k"], E2E["train"]), 1)
     outs = _cfar(s, cfg, iq_t, E)
-    segs = _Segs.from_masks(s, outs["mask"], outs["spectrum"], E2E["merge_gap"], E2E["min_width"], E2E["max_segments"])
-    got = _tracks(s, segs, eps, E2E["slack_bins"], E2E["max_miss"], E2E["min_epochs"], E2E["max_tracks"]).host()
+    segs = tu.Segs.from_masks(s, outs["mask"], outs["spectrum"], E2E["merge_gap"], E2E["min_width"], E2E["max_segments"])
+    got = tu.tracks(s, segs, eps, E2E["slack_bins"], E2E["max_miss"], E2E["min_epochs"], E2E["max_tracks"]).host()
     truth = truth_t.cpu().numpy().reshape(n_streams, eps)
     ep, _ = segs.host()
     s.close()
@@ -327,46 +251,26 @@ MARGIN = 1.06
 
 def test_cost_next_to_cfar_and_segments(built):
     """N = 4096, K = 10, rect, 64 bands, the 2.18 GB batch of 6656 epochs, 16 slots, the traffic of tests/test_segments_gpu.py's speed
-    test; each timed window holds 8 launches issued back to back behind one already queued, the arms alternate, 5 windows each after a
-    warm-up, the best counts.  Printed, not asserted: the stage alone on the same segments plus one emitter that stays in bins 324..326 of
+    test; the method of tests/stage_gpu.py (best_of_windows): each timed window holds 8 launches issued back to back behind one already
+    queued, the arms alternate, 5 windows each after a warm-up, the best counts.  Printed, not asserted: the stage alone on the same segments plus one emitter that stays in bins 324..326 of
     every epoch, a track as long as the stream, where the members' atomic adds to one accumulator queue up."""
     n, k = 4096, 10
-    cfg = _cfg(n, k, bands=64)
+    cfg = sgpu.cfg(n, k=k, bands=64)
     E, S = 6656, 16
-    gen = torch.Generator(device=DEV)
-    gen.manual_seed(5)
-    iq_t = torch.randn(E * k * n * 2, generator=gen, device=DEV, dtype=torch.float32)
-    t = torch.arange(n, device=DEV, dtype=torch.float32)
-    frames = iq_t.view(E, k, n, 2)
-    for j, b in enumerate((300, 301, 302, 303, 1600, 1601, 1602, 3000)):
-        ph = 2 * np.pi * ((b * t) % n) / n
-        sel = slice(j % 3, E, 3)
-        frames[sel, :, :, 0] += 0.3 * torch.cos(ph)
-        frames[sel, :, :, 1] += 0.3 * torch.sin(ph)
+    iq_t = sgpu.add_tones(sgpu.noise_batch(E, k, n), E, k, n)
     s = cs.Sensor(cfg)
     s.set_cfar(G_, W_, cs.cfar_alpha(1e-3, k, W_), 1)
     outs = _cfar(s, cfg, iq_t, E)
-    segs = _Segs(E, S)
-    out = {64: _Tracks(E, S, 64, 64), 1: _Tracks(E, S, 1, 64)}
+    segs = tu.Segs(E, S)
+    out = {64: tu.Tracks(E, S, 64, 64), 1: tu.Tracks(E, S, 1, 64)}
     torch.cuda.synchronize()
-    R = 8
-
-    def timed(fn):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        fn()
-        a.record()
-        for _ in range(R):
-            fn()
-        b.record()
-        b.synchronize()
-        return a.elapsed_time(b) / R
 
     def arm_a():
         _cfar(s, cfg, iq_t, E, outs=outs)
         s.segments_device(outs["mask"].data_ptr(), outs["spectrum"].data_ptr(), E, segs.epochs.data_ptr(), segs.segments.data_ptr(), max_segments=S)
 
     def alone(ns):
-        _tracks(s, segs, E // ns, 1, 0, 1, 64, out=out[ns])
+        tu.tracks(s, segs, E // ns, 1, 0, 1, 64, out=out[ns])
 
     def arm_b(ns):
         arm_a()
@@ -374,26 +278,20 @@ def test_cost_next_to_cfar_and_segments(built):
     arm_a()
     stay = outs["mask"].clone()
     stay[:, 10] |= 0x70
-    segs_stay = _Segs.from_masks(s, stay, outs["spectrum"], 0, 1, S)
+    segs_stay = tu.Segs.from_masks(s, stay, outs["spectrum"], 0, 1, S)
 
     def alone_stay(ns):
-        _tracks(s, segs_stay, E // ns, 1, 0, 1, 64, out=out[ns])
+        tu.tracks(s, segs_stay, E // ns, 1, 0, 1, 64, out=out[ns])
     arms = {"A": arm_a, "B 64": lambda: arm_b(64), "B 1": lambda: arm_b(1), "alone 64": lambda: alone(64), "alone 1": lambda: alone(1)}
-    for fn in arms.values():
-        fn()
-    torch.cuda.synchronize()
-    times = {name: [] for name in arms}
-    for _ in range(5):
-        for name, fn in arms.items():
-            times[name].append(timed(fn))
+    times = sgpu.best_of_windows(arms)
     st64, st1 = out[64].host()[0], out[1].host()[0]
     ep = segs.host()[0]
-    stay_us = {ns: min(timed(lambda: alone_stay(ns)) for _ in range(3)) * 1e3 for ns in (64, 1)}
+    stay_us = {}
+    for ns in (64, 1):
+        stay_us[ns] = min(sgpu.best_of_windows({ns: lambda: alone_stay(ns)}, windows=3, warm_up=False, report=False)[ns]) * 1e3
     longest = int(out[1].host()[1]["n_epochs_hit"].max())
     s.close()
     best = {name: min(v) for name, v in times.items()}
-    for name, v in times.items():
-        print(f"ms per launch, {name}:", " ".join(f"{x:.4f}" for x in v))
     r64, r1, one_over_64 = best["B 64"] / best["A"], best["B 1"] / best["A"], best["alone 1"] / best["alone 64"]
     print(f"N=4096 K=10 rect 64 bands, {E} epochs, {S} slots, {int(ep['n_stored'].sum())} nodes; tracks found: {int(st64['n_found'].sum())} in 64 "
           f"streams, {int(st1['n_found'].sum())} in one; arm A (CFAR + segments) {best['A']:.4f} ms")

@@ -12,6 +12,7 @@ import pytest
 
 import crnsense as cs
 import tracks_f64 as tk
+from tracks_cases import E2E, check_end_to_end, e2e_cfg, e2e_synth, runs_of_truth
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 N = 256
@@ -132,77 +133,6 @@ def test_no_link_across_a_stream_boundary_and_the_flags():
 
 
 # ---- the chain on the twins -------------------------------------------------------------------------------------------------
-# The parameters of the end-to-end test, chosen here: the headline plan (N = 4096, K = 10, rectangular window), CRN_SIG_CW (one
-# on-grid bin on the rectangular window, so min_width = 1 and no closing), CA-CFAR guard 2 / train 16 at Pfa 1e-6: with 4096 bins
-# and 6656 epochs that leaves some tens of single-bin false alarms in the batch, and two of them in touching bins of consecutive
-# epochs (which would make a second track of two epochs) are expected 6656 x 4096 x 3 x 1e-12 = 1e-4 times.
-E2E = {"n": 4096, "k": 10, "guard": 2, "train": 16, "pfa": 1e-6, "merge_gap": 0, "min_width": 1, "max_segments": 16, "slack_bins": 1,
-       "max_miss": 0, "min_epochs": 1, "max_tracks": 256, "signal_kind": cs.SIG_CW, "noise_power": 1e-6, "signal_rms": 0.02, "seed": 2027,
-       "eps": 104}
-
-
-def e2e_cfg():
-    c = cs.cfg_energy_scaled(E2E["n"])
-    c.window, c.hop, c.frames_per_epoch = cs.WINDOW_RECT, E2E["n"], E2E["k"]
-    return c
-
-
-def e2e_synth(n_streams):
-    sc = cs.SynthCfg()
-    sc.seed, sc.noise_power, sc.signal_rms = E2E["seed"], E2E["noise_power"], E2E["signal_rms"]
-    sc.tones_per_band, sc.pu_model, sc.signal_kind, sc.n_streams = 8, cs.PU_MARKOV_INTENDED, E2E["signal_kind"], n_streams
-    return sc
-
-
-def band_of_bin(cfg, k):
-    k = int(np.floor(k)) % cfg.fft_len
-    for s in range(cfg.n_segs):
-        if cfg.segs[s].lo <= k < cfg.segs[s].hi:
-            return cfg.segs[s].band
-    return -1
-
-
-def runs_of_truth(truth_row):
-    """[(band, first_t, last_t)] of the maximal runs of one stream's truth."""
-    cuts = np.flatnonzero(np.diff(truth_row)) + 1
-    starts, ends = np.r_[0, cuts], np.r_[cuts, truth_row.size]
-    return [(int(truth_row[a]), int(a), int(b - 1)) for a, b in zip(starts, ends)]
-
-
-def check_end_to_end(cfg, truth, streams, tracks):
-    """The condition of the end-to-end test on one batch: truth [n_streams][eps]; streams / tracks as the kernel or the twin gives them.
-    Returns (dwell runs, single-epoch other tracks)."""
-    n_streams, eps = truth.shape
-    n_runs = n_other = 0
-    for st in range(n_streams):
-        assert streams["n_found"][st] == streams["n_stored"][st], "max_tracks too small for this batch"
-        trs = tracks[st, : streams["n_stored"][st]]
-        bands = np.array([band_of_bin(cfg, t["centre"]) for t in trs])
-        matched = np.zeros(trs.size, bool)
-        seq = []
-        for band, a, b in runs_of_truth(truth[st]):
-            if band == 0:
-                continue
-            hit = np.flatnonzero((bands == band) & (trs["first_t"] == a) & (trs["last_t"] == b))
-            assert hit.size == 1, (st, band, a, b, hit, [(int(t["first_t"]), int(t["last_t"]), float(t["centre"])) for t in trs])
-            matched[hit[0]] = True
-            seq.append((int(trs["first_t"][hit[0]]), band, b - a + 1))
-            n_runs += 1
-        assert (trs["n_epochs_hit"][~matched] == 1).all(), (st, trs[~matched])
-        n_other += int((~matched).sum())
-        # the 3 x 3 transition counts rebuilt from the matched tracks in time order against those counted in the truth
-        seq.sort()
-        got = np.zeros((4, 4), np.int64)
-        for i, (_, band, length) in enumerate(seq):
-            got[band, band] += length - 1
-            if i + 1 < len(seq):
-                got[band, seq[i + 1][1]] += 1
-        want = np.zeros((4, 4), np.int64)
-        np.add.at(want, (truth[st][:-1], truth[st][1:]), 1)
-        assert (got == want).all(), (st, got, want)
-    return n_runs, n_other
-
-
 def test_chain_on_the_twins_finds_every_dwell_run(built):
     """8 streams x 104 epochs of the intended Markov chain from the C oracle's generator, through the oracle's spectrum, the CFAR twin,
     the segments twin and the tracks twin with the E2E parameters: every dwell run is exactly one track, every other track lives one
