@@ -791,6 +791,61 @@ CRN_API int crn_tcfar_device(crn_handle *h, const float *d_spectrum, int64_t n_e
                              const uint32_t *d_or_mask, uint32_t *d_bin_mask, crn_tcfar_row *d_rows, float *d_hist, int64_t *d_seen,
                              void *stream);
 
+/* -- what a segment is: occupied bandwidth, x-dB bandwidth and shape --------------------------------------------------------------
+ * crn_segments_device gives the mask's idea of an emitter; its width is the width of the detected bits plus what merge_gap closed and
+ * moves with the false-alarm rate.  This stage measures each stored segment on its own `spectrum` row with the two widths spectrum
+ * monitoring quotes: the occupied bandwidth, the span that holds all but a small share of the power (ITU-R SM.443's beta / 2 rule), and
+ * the x-dB bandwidth, the outermost points that still rise above peak - x dB.  With the crest they tell a carrier from a flat wideband
+ * signal from a multicarrier.  The powers of a segment are turned into integers once and every sum is an integer sum, so the result
+ * has no rounding freedom: it is the same in any order of addition.  N = fft_len, fl32(.) is one fp32 operation.
+ * Per epoch e, for each slot s < min(max(d_epochs[e].n_stored, 0), max_segments) of d_segments[e], with row P and lo, width = w and
+ * peak_power from the record:
+ *   1. noise     nm = the epoch's noise_mean if subtract_noise is set and it is finite and > 0, otherwise 0.
+ *   2. net bins  Q[i] = fl32(P[(lo + i) mod N] - nm), 0 <= i < w; Q[i] counts as 0 unless Q[i] > 0 (NaN included).
+ *                pq = fl32(peak_power - nm).
+ *   3. integers  e = the binary exponent of peak_power (2^e <= peak_power < 2^(e+1), subnormals included: frexp's, less one).
+ *                q[i] = min(trunc(Q[i] 2^(30 - e)), 2^31 - 1): a scaling by a power of two, exact.  q[i] < 2^31, S0 = sum q < 2^43 and
+ *                S0 tail_ppm < 2^62: every sum is an exact integer in int64 (and in fp64).
+ *   4. occupied  T = (S0 tail_ppm) div 10^6, C[i] = q[0] + .. + q[i], C[-1] = 0.  obw_lo = the smallest i with C[i] > T; the last bin
+ *                is the largest i with S0 - C[i-1] > T; obw_width = last - obw_lo + 1, >= 1 whenever S0 > 0 (T < S0 / 2).
+ *   5. x dB      thr = fl32(xdb_ratio pq).  A bin is above when Q[i] > thr, strictly.  xdb_lo = the first such i, xdb_width spans to
+ *                the last one, n_above = their count (none above: all three are 0).  n_above / xdb_width is the fill: 1 for a solid
+ *                emitter, less for a multicarrier.
+ *   6. floats    net_power = fl32(S0 2^(e - 30)); crest = fl32((double) max q w / (double) S0), one fp64 division rounded to fp32: near
+ *                w for a carrier, near 1 for a flat emitter.
+ *   7. nothing   the whole record is zero bytes when lo is outside 0 .. N - 1, width outside 1 .. N, peak_power not finite or not > 0,
+ *                pq not > 0, or S0 = 0.  Slots at and beyond n_stored are zero-filled, as crn_segments_device does: a batch gives
+ *                the same bytes however it is cut into launches.  obw_width == 0 is the caller's test for "not measured".
+ * Offsets count from the segment's own lo, like centroid: the absolute bin is (lo + obw_lo) mod N.
+ *   Limits       the clamp at 0 keeps the half of the noise's fluctuation that lies above noise_mean, so a weak lone carrier's
+ *                99 % width is several bins and not 1; a record whose peak_power is not its row's (a foreign array) measures
+ *                against that peak_power and costs wrong numbers, nothing else. */
+typedef struct crn_measure_params {
+  int32_t max_segments;   /* as given to crn_segments_device: 1 .. 256 */
+  int32_t tail_ppm;       /* share of the net power left outside on EACH side, in 1e-6: 0 .. 499999 (SM.443's 99 %: 5000) */
+  float xdb_ratio;        /* linear power ratio of the x-dB rule, finite, 0 <= r < 1 (26 dB: 10^-2.6) */
+  int32_t subtract_noise; /* 0 | 1: take the epoch's noise_mean off every bin first */
+  int32_t reserved[4];    /* 0 */
+} crn_measure_params; /* 32 bytes */
+typedef struct crn_measure {
+  int32_t obw_lo, obw_width, xdb_lo, xdb_width; /* offsets count from the segment's own lo */
+  int32_t n_above;
+  float net_power, crest, reserved;
+} crn_measure; /* 32 bytes */
+
+/* Enqueue the measurement on `stream` over n_epochs rows, one launch (device pointers, all 16-byte aligned):
+ *   d_spectrum  [n_epochs][fft_len]        the rows the segments were cut from
+ *   d_epochs    [n_epochs]                 the headers crn_segments_device wrote (n_stored and noise_mean are read)
+ *   d_segments  [n_epochs][max_segments]   its records (lo, width and peak_power are read)
+ *   d_measures  [n_epochs][max_segments]   one record per slot, every slot written
+ * `h` supplies fft_len and the device, nothing else.  Allocates nothing, keeps no state, needs no workspace.  Whatever bytes d_epochs
+ * and d_segments hold, only the epoch's own row and records are read and only its own max_segments slots written.  CRN_ERR_ARG for a
+ * NULL h, params, d_spectrum, d_epochs, d_segments or d_measures; max_segments outside 1 .. 256; tail_ppm outside 0 .. 499999; an
+ * xdb_ratio that is not finite or outside [0, 1); subtract_noise other than 0 or 1; a nonzero reserved; n_epochs < 0; any of the four
+ * arrays not 16-byte aligned.  n_epochs = 0 succeeds and touches nothing. */
+CRN_API int crn_measure_device(crn_handle *h, const float *d_spectrum, int64_t n_epochs, const crn_measure_params *params,
+                               const crn_segment_epoch *d_epochs, const crn_segment *d_segments, crn_measure *d_measures, void *stream);
+
 /* Allocate, now, the device scratch and pinned staging that crn_sense_run_host needs for up to
  * max_epochs dense epochs of full-length frames (and their per-bin spectra when want_spectrum != 0),
  * and load the kernels: a later crn_sense_run_host within that size allocates nothing.  An engine

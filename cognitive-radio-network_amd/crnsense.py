@@ -53,6 +53,7 @@ EXPORTS = [
     "crn_holes_workspace_bytes", "crn_holes_device",
     "crn_lad_device", "crn_lad_factor",
     "crn_tcfar_hist_bytes", "crn_tcfar_device",
+    "crn_measure_device",
     "crn_comm_unique_id", "crn_comm_create", "crn_comm_local", "crn_comm_allgather", "crn_comm_gathered",
     "crn_comm_finish", "crn_comm_destroy", "crn_comm_local_addr", "crn_comm_wait", "crn_comm_info",
     "crn_last_error", "crn_abi_version", "crn_build_info",
@@ -228,6 +229,18 @@ class TcfarRow(C.Structure):
 
 # numpy view of the headers crn_tcfar_device writes: np.frombuffer(bytes, TCFAR_ROW_DTYPE), one per epoch
 TCFAR_ROW_DTYPE = [("n_detected", "<i4"), ("n_new", "<i4"), ("n_cells", "<i4"), ("reserved", "<i4")]
+
+
+class MeasureParams(C.Structure):
+    """crn_measure_params (crn_measure_device), 32 bytes."""
+    _fields_ = [("max_segments", C.c_int32), ("tail_ppm", C.c_int32), ("xdb_ratio", C.c_float), ("subtract_noise", C.c_int32),
+                ("reserved", C.c_int32 * 4)]
+
+
+# numpy view of the records crn_measure_device writes: np.frombuffer(bytes, MEASURE_DTYPE).reshape(n_epochs, max_segments), slot by slot
+# next to SEGMENT_DTYPE's; offsets count from the segment's own lo
+MEASURE_DTYPE = [("obw_lo", "<i4"), ("obw_width", "<i4"), ("xdb_lo", "<i4"), ("xdb_width", "<i4"), ("n_above", "<i4"), ("net_power", "<f4"),
+                 ("crest", "<f4"), ("reserved", "<f4")]
 CFAR_METHODS = {"ca": CFAR_CA, "go": CFAR_GO, "so": CFAR_SO, "os": CFAR_OS}
 
 
@@ -367,6 +380,7 @@ def lib():
         L.crn_tcfar_hist_bytes.argtypes, L.crn_tcfar_hist_bytes.restype = [C.c_int64, C.c_int32, C.POINTER(TcfarParams)], C.c_int64
         L.crn_tcfar_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(TcfarParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.c_void_p]
+        L.crn_measure_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(MeasureParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.crn_ingest_create.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]
         L.crn_ingest_push.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
         L.crn_ingest_flush.argtypes = [C.c_void_p]
@@ -622,6 +636,28 @@ def tcfar_hist_bytes(n_streams, fft_len, params):
     if nb <= 0:
         raise CrnError(f"crn_tcfar_hist_bytes: arguments out of range ({nb})")
     return nb
+
+
+def xdb_ratio(db):
+    """The linear power ratio of an x-dB rule, 10^(-db / 10), for crn_measure_params.xdb_ratio: 26 dB gives 10^-2.6."""
+    return 10.0 ** (-float(db) / 10.0)
+
+
+def measure_params(max_segments=16, obw_percent=99.0, xdb=26.0, subtract_noise=True):
+    """crn_measure_params: max_segments as given to the segment stage; obw_percent the share of the net power inside the occupied
+    bandwidth, split evenly between the two tails (99 % leaves 5000 ppm on each side); xdb the depth of the x-dB rule in dB."""
+    return MeasureParams(max_segments=int(max_segments), tail_ppm=int(round((100.0 - float(obw_percent)) * 5000.0)), xdb_ratio=xdb_ratio(xdb),
+                         subtract_noise=int(bool(subtract_noise)))
+
+
+def measure_hz(lo, obw_lo, obw_width, xdb_lo, xdb_width, fft_len, fs, fc):
+    """((centre frequency, occupied bandwidth), (centre frequency, x-dB bandwidth)) in Hz of a record from crn_measure_device and the lo
+    of its segment: each centre is the middle of its span, at bin lo + offset + (width - 1) / 2, and the mapping of bins to hertz is
+    segment_hz's, so a span that crosses the wrap comes out around fc.  A width of 0 (not measured, or no bin above the line) gives
+    a bandwidth of 0 at the segment's first bin."""
+    def span(off, width):
+        return segment_hz(lo, width, float(off) + max(float(width) - 1.0, 0.0) / 2.0, fft_len, fs, fc)
+    return span(obw_lo, obw_width), span(xdb_lo, xdb_width)
 
 
 def hole_hz(lo, width, fft_len, fs, fc):
@@ -956,6 +992,14 @@ class Sensor:
         v = lambda ptr: C.c_void_p(ptr or None)      # noqa: E731
         check(lib().crn_tcfar_device(self._h, v(spectrum_ptr), n_epochs, C.byref(params), v(or_mask_ptr), v(mask_ptr), v(rows_ptr), v(hist_ptr),
                                      v(seen_ptr), v(stream)), "crn_tcfar_device")
+
+    def measure_device(self, spectrum_ptr, n_epochs, params, epochs_ptr, segments_ptr, measures_ptr, stream=None):
+        """Occupied bandwidth, x-dB bandwidth and shape of every stored segment of n_epochs rows (device pointers; params from
+        measure_params): spectrum_ptr [n_epochs][fft_len] float32, epochs_ptr and segments_ptr what segments_device wrote with the same
+        max_segments, measures_ptr [n_epochs][max_segments] MEASURE_DTYPE, every slot written.  Only enqueues."""
+        v = lambda ptr: C.c_void_p(ptr or None)      # noqa: E731
+        check(lib().crn_measure_device(self._h, v(spectrum_ptr), n_epochs, C.byref(params), v(epochs_ptr), v(segments_ptr), v(measures_ptr),
+                                       v(stream)), "crn_measure_device")
 
     def fuse_device(self, mask_ptr, spectrum_ptr, n_epochs, params, fused_mask_ptr=0, fused_spectrum_ptr=0, rows_ptr=0, stream=0):
         """Fuses groups of params.group_size streams (fuse_params; device pointers): mask_ptr [n_epochs][fft_len / 32] uint32 and
