@@ -846,6 +846,89 @@ typedef struct crn_measure {
 CRN_API int crn_measure_device(crn_handle *h, const float *d_spectrum, int64_t n_epochs, const crn_measure_params *params,
                                const crn_segment_epoch *d_epochs, const crn_segment *d_segments, crn_measure *d_measures, void *stream);
 
+/* -- occupancy map: what every bin did over time -------------------------------------------------------------------------------
+ * The occupancy survey of spectrum monitoring (ITU-R SM.2256), per bin: how often each frequency is occupied, how often it changes
+ * state and how long it stays busy or idle, the highest and lowest level seen there (max hold, min hold), and the mean level while
+ * idle and while busy.  The mean level while idle, power[0] / (n_epochs - n_busy), is the receiver's noise floor bin by bin: its shape,
+ * which noise_mean of the segment stage and the floor of crn_lad_device, one number per row or block, cannot show.
+ * crn_channels_device keeps such a record for at most 64 spans named in advance and crn_holes_device one number per bin; this stage
+ * keeps one record per stream and bin, in the caller's device memory, its own carry from call to call.  A batch is laid out as for
+ * crn_tracks_device: S = n_epochs / epochs_per_stream streams of T = epochs_per_stream epochs in time order; N = fft_len.
+ * For stream j, bin k and epoch t: s = bit k of the mask row; P = the `spectrum` value (0 when d_spectrum is NULL); u = the bit pattern
+ * of P as uint32 (0 when d_spectrum is NULL).  For the non-negative values a power row holds, unsigned order of u is numeric order,
+ * +inf lies above every finite value and NaN above that; umax and umin below compare u, so a negative value, which no power row
+ * holds, counts as above every positive one.  sat(x) = min(x, 2^31 - 1).  The sequential rule is the definition:
+ *       R = the carried record; taken as all zero when params.first != 0 or R.n_epochs <= 0
+ *       R.run = max(R.run, 0)
+ *       for each epoch of the stream in time order:
+ *           if R.n_epochs > 0:
+ *               a = R.state & 1
+ *               if s != a:
+ *                   if a == 0: R.n_rise = sat(R.n_rise + 1)
+ *                   else:      R.n_fall = sat(R.n_fall + 1)
+ *                   R.run_max[a] = max(R.run_max[a], R.run); R.run = 0
+ *               R.max_hold = umax(R.max_hold, u); R.min_hold = umin(R.min_hold, u)
+ *           else:
+ *               R.max_hold = R.min_hold = u
+ *           R.state = s; R.run = sat(R.run + 1); R.n_epochs = sat(R.n_epochs + 1)
+ *           R.n_busy = sat(R.n_busy + s); R.power[s] += (double)P
+ *       R.reserved = 0
+ *     The first run starts with the first observed epoch (it is left-censored) and is counted when it ends, as in crn_channel_stats;
+ *     the run in progress is in no completed figure.  No index is ever read from a record: whatever bytes the carry holds, the call
+ *     reads and writes only its own arrays.
+ *   Usual mask     d_usual_mask [S][N / 32], optional, in the bit layout of the bin mask: bit k is set when n_epochs > 0 and
+ *                  (int64)n_busy 10^6 >= (int64)duty_ppm n_epochs, on the record as the call leaves it.  It is the band plan of the
+ *                  emitters that are usually there, and feeds crn_segments_device, crn_holes_device and crn_channels_device unchanged.
+ *   Header         one crn_occmap_stream per stream: busy_sum = the sum of n_busy over the bins; n_epochs = that of bin 0;
+ *                  usual_bins = the bits of the usual mask, counted whether or not the mask is asked for; clear_bins = bins with
+ *                  n_busy == 0; busy_now = bins with state & 1 set.
+ *   Cut independence   a stream given in one call and the same stream cut into several calls (first = 1, then 0) give identical
+ *                  integer fields, state, max_hold and min_hold, an identical usual mask and identical headers.  power[] is an fp64
+ *                  sum whose order depends on the cut and on the kernels' chunks of 64 epochs: within n_epochs 2^-52 relative of the
+ *                  exact sum for non-negative rows.  Within one build the same call repeated gives the same bytes, power[] included
+ *                  (a fixed order, no floating-point atomics). */
+typedef struct crn_occmap_params {
+  int32_t epochs_per_stream; /* >= 1, divides n_epochs */
+  int32_t first;             /* != 0: the records' contents mean nothing, start afresh */
+  int32_t duty_ppm;          /* 1 .. 1000000: the busy fraction, in 1e-6, from which a bin is in the usual mask */
+  int32_t reserved[5];       /* 0 */
+} crn_occmap_params; /* 32 bytes */
+typedef struct crn_occmap_bin {
+  int32_t n_epochs, n_busy;
+  int32_t n_rise, n_fall;    /* idle->busy, busy->idle transitions */
+  int32_t run, state;        /* length of the run in progress; bit 0 of state = the last epoch's s */
+  int32_t run_max[2];        /* longest COMPLETED idle / busy run */
+  float max_hold, min_hold;  /* compared as uint32 bit patterns */
+  int32_t reserved[2];       /* written as 0 */
+  double power[2];           /* fp64 sum of P over idle / busy epochs */
+} crn_occmap_bin; /* 64 bytes */
+typedef struct crn_occmap_stream {
+  int64_t busy_sum;
+  int32_t n_epochs, usual_bins, clear_bins, busy_now;
+  int32_t reserved[2];       /* written as 0 */
+} crn_occmap_stream; /* 32 bytes */
+
+/* Bytes of device scratch crn_occmap_device needs for n_epochs epochs under `params`: needs no handle and no device (it is sized for
+ * the largest fft_len).  Positive for valid arguments (also for n_epochs = 0), -1 for a NULL params, n_epochs < 0, epochs_per_stream
+ * < 1 or not dividing n_epochs, duty_ppm outside 1 .. 1000000, or a nonzero reserved. */
+CRN_API int64_t crn_occmap_workspace_bytes(int64_t n_epochs, const crn_occmap_params *params);
+
+/* Enqueue the stage on `stream`, three launches (device pointers):
+ *   d_bin_mask    [n_epochs][fft_len / 32]     as crn_sense_run_device_cfar writes it (8-byte aligned)
+ *   d_spectrum    [n_epochs][fft_len]          the `spectrum` output of the same launch (16-byte aligned), or NULL: P = 0 and u = 0
+ *   d_bins        [n_streams][fft_len]         the records (16-byte aligned): read (unless first != 0), then rewritten
+ *   d_streams     [n_streams]                  the headers (16-byte aligned)
+ *   d_usual_mask  [n_streams][fft_len / 32]    or NULL (8-byte aligned)
+ *   d_workspace   workspace_bytes >= crn_occmap_workspace_bytes of scratch (16-byte aligned); its contents before and after mean nothing
+ * `h` supplies fft_len and the device, nothing else: the mask and rows may come from any source, the handle may be of any mode, with
+ * CFAR on or off.  Only enqueues, allocates nothing, keeps no host state.  CRN_ERR_ARG, decided before any device call, for a NULL h,
+ * params, d_bin_mask, d_bins, d_streams or d_workspace; n_epochs < 0; epochs_per_stream < 1 or not dividing n_epochs; duty_ppm outside
+ * 1 .. 1000000; a nonzero reserved field; a misaligned pointer; a workspace too small.  n_epochs = 0 succeeds and touches nothing,
+ * with first != 0 too (the records are then left as they are). */
+CRN_API int crn_occmap_device(crn_handle *h, const uint32_t *d_bin_mask, const float *d_spectrum, int64_t n_epochs,
+                              const crn_occmap_params *params, crn_occmap_bin *d_bins, crn_occmap_stream *d_streams,
+                              uint32_t *d_usual_mask, void *d_workspace, int64_t workspace_bytes, void *stream);
+
 /* Allocate, now, the device scratch and pinned staging that crn_sense_run_host needs for up to
  * max_epochs dense epochs of full-length frames (and their per-bin spectra when want_spectrum != 0),
  * and load the kernels: a later crn_sense_run_host within that size allocates nothing.  An engine

@@ -54,6 +54,7 @@ EXPORTS = [
     "crn_lad_device", "crn_lad_factor",
     "crn_tcfar_hist_bytes", "crn_tcfar_device",
     "crn_measure_device",
+    "crn_occmap_workspace_bytes", "crn_occmap_device",
     "crn_comm_unique_id", "crn_comm_create", "crn_comm_local", "crn_comm_allgather", "crn_comm_gathered",
     "crn_comm_finish", "crn_comm_destroy", "crn_comm_local_addr", "crn_comm_wait", "crn_comm_info",
     "crn_last_error", "crn_abi_version", "crn_build_info",
@@ -241,6 +242,19 @@ class MeasureParams(C.Structure):
 # next to SEGMENT_DTYPE's; offsets count from the segment's own lo
 MEASURE_DTYPE = [("obw_lo", "<i4"), ("obw_width", "<i4"), ("xdb_lo", "<i4"), ("xdb_width", "<i4"), ("n_above", "<i4"), ("net_power", "<f4"),
                  ("crest", "<f4"), ("reserved", "<f4")]
+
+
+class OccmapParams(C.Structure):
+    """crn_occmap_params (crn_occmap_device), 32 bytes."""
+    _fields_ = [("epochs_per_stream", C.c_int32), ("first", C.c_int32), ("duty_ppm", C.c_int32), ("reserved", C.c_int32 * 5)]
+
+
+# numpy views of what crn_occmap_device keeps and writes: (.., OCCMAP_BIN_DTYPE).reshape(n_streams, fft_len), one 64-byte record per
+# stream and bin, its own carry; (.., OCCMAP_STREAM_DTYPE) [n_streams], the headers
+OCCMAP_BIN_DTYPE = [("n_epochs", "<i4"), ("n_busy", "<i4"), ("n_rise", "<i4"), ("n_fall", "<i4"), ("run", "<i4"), ("state", "<i4"),
+                    ("run_max", "<i4", (2,)), ("max_hold", "<f4"), ("min_hold", "<f4"), ("reserved", "<i4", (2,)), ("power", "<f8", (2,))]
+OCCMAP_STREAM_DTYPE = [("busy_sum", "<i8"), ("n_epochs", "<i4"), ("usual_bins", "<i4"), ("clear_bins", "<i4"), ("busy_now", "<i4"),
+                       ("reserved", "<i4", (2,))]
 CFAR_METHODS = {"ca": CFAR_CA, "go": CFAR_GO, "so": CFAR_SO, "os": CFAR_OS}
 
 
@@ -381,6 +395,9 @@ def lib():
         L.crn_tcfar_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(TcfarParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.c_void_p]
         L.crn_measure_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(MeasureParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.crn_occmap_workspace_bytes.argtypes, L.crn_occmap_workspace_bytes.restype = [C.c_int64, C.POINTER(OccmapParams)], C.c_int64
+        L.crn_occmap_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(OccmapParams), C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.c_void_p, C.c_int64, C.c_void_p]
         L.crn_ingest_create.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]
         L.crn_ingest_push.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
         L.crn_ingest_flush.argtypes = [C.c_void_p]
@@ -658,6 +675,45 @@ def measure_hz(lo, obw_lo, obw_width, xdb_lo, xdb_width, fft_len, fs, fc):
     def span(off, width):
         return segment_hz(lo, width, float(off) + max(float(width) - 1.0, 0.0) / 2.0, fft_len, fs, fc)
     return span(obw_lo, obw_width), span(xdb_lo, xdb_width)
+
+
+def occmap_params(epochs_per_stream, duty=0.5, first=False):
+    """crn_occmap_params: `duty` is the busy fraction from which a bin enters the usual mask, kept in parts per million."""
+    return OccmapParams(epochs_per_stream=int(epochs_per_stream), first=int(bool(first)), duty_ppm=int(round(float(duty) * 1e6)))
+
+
+def occmap_workspace_bytes(n_epochs, epochs_per_stream=None, duty=0.5):
+    """Bytes of device scratch Sensor.occmap_device needs (crn_occmap_workspace_bytes): no handle, no device."""
+    q = occmap_params(n_epochs if epochs_per_stream is None else epochs_per_stream, duty)
+    nb = lib().crn_occmap_workspace_bytes(int(n_epochs), C.byref(q))
+    if nb < 0:
+        raise CrnError(f"crn_occmap_workspace_bytes: arguments out of range ({nb})")
+    return nb
+
+
+def occupancy_map(records):
+    """What the records of crn_occmap_device (OCCMAP_BIN_DTYPE, any shape) say per bin, as a dict of arrays of that shape: `duty` =
+    n_busy / n_epochs (the frequency channel occupancy), `rise_rate` = n_rise / n_epochs (idle -> busy transitions per epoch),
+    `mean_idle` = power[0] / (n_epochs - n_busy) (the noise floor's shape) and `mean_busy` = power[1] / n_busy, each 0 where its count
+    is 0; `max_hold` and `min_hold` as they are."""
+    import numpy as np
+    r = np.asarray(records)
+    n, nb = r["n_epochs"].astype(np.float64), r["n_busy"].astype(np.float64)
+
+    def over(num, den):
+        return np.divide(num, den, out=np.zeros(r.shape, np.float64), where=den > 0)
+    return {"duty": over(nb, n), "rise_rate": over(r["n_rise"].astype(np.float64), n), "mean_idle": over(r["power"][..., 0], n - nb),
+            "mean_busy": over(r["power"][..., 1], nb), "max_hold": r["max_hold"].copy(), "min_hold": r["min_hold"].copy()}
+
+
+def floor_db(records, fallback=None):
+    """The noise floor per bin in dB, 10 log10 of occupancy_map's mean_idle.  A bin never seen idle, or whose idle mean is not positive,
+    has no floor of its own: it takes `fallback` (dB), NaN when that is None."""
+    import numpy as np
+    m = occupancy_map(records)["mean_idle"]
+    out = np.full(m.shape, np.nan if fallback is None else float(fallback), np.float64)
+    np.log10(m, out=out, where=m > 0)
+    return np.where(m > 0, 10.0 * out, out)
 
 
 def hole_hz(lo, width, fft_len, fs, fc):
@@ -1000,6 +1056,17 @@ class Sensor:
         v = lambda ptr: C.c_void_p(ptr or None)      # noqa: E731
         check(lib().crn_measure_device(self._h, v(spectrum_ptr), n_epochs, C.byref(params), v(epochs_ptr), v(segments_ptr), v(measures_ptr),
                                        v(stream)), "crn_measure_device")
+
+    def occmap_device(self, mask_ptr, spectrum_ptr, n_epochs, bins_ptr, streams_ptr, workspace_ptr, workspace_bytes, epochs_per_stream=None,
+                      duty=0.5, first=False, usual_mask_ptr=0, stream=None):
+        """The occupancy map of n_epochs rows of a CFAR bin mask and, unless spectrum_ptr is 0, the matching `spectrum` rows (device
+        pointers): bins_ptr [n_streams][fft_len] OCCMAP_BIN_DTYPE, read unless first and then rewritten; streams_ptr [n_streams]
+        OCCMAP_STREAM_DTYPE; usual_mask_ptr [n_streams][fft_len / 32] uint32 or 0, the bins busy in at least `duty` of their epochs;
+        workspace_ptr at least occmap_workspace_bytes(...) of scratch.  One stream unless epochs_per_stream is given.  Only enqueues."""
+        q = occmap_params(n_epochs if epochs_per_stream is None else epochs_per_stream, duty, first)
+        v = lambda ptr: C.c_void_p(ptr or None)      # noqa: E731
+        check(lib().crn_occmap_device(self._h, v(mask_ptr), v(spectrum_ptr), n_epochs, C.byref(q), v(bins_ptr), v(streams_ptr), v(usual_mask_ptr),
+                                      v(workspace_ptr), int(workspace_bytes), v(stream)), "crn_occmap_device")
 
     def fuse_device(self, mask_ptr, spectrum_ptr, n_epochs, params, fused_mask_ptr=0, fused_spectrum_ptr=0, rows_ptr=0, stream=0):
         """Fuses groups of params.group_size streams (fuse_params; device pointers): mask_ptr [n_epochs][fft_len / 32] uint32 and
