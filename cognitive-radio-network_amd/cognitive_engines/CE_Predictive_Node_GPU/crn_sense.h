@@ -846,6 +846,84 @@ typedef struct crn_measure {
 CRN_API int crn_measure_device(crn_handle *h, const float *d_spectrum, int64_t n_epochs, const crn_measure_params *params,
                                const crn_segment_epoch *d_epochs, const crn_segment *d_segments, crn_measure *d_measures, void *stream);
 
+/* -- what a segment is: the symbol rate from the cyclic spectrum ---------------------------------------------------------------------
+ * Every stage above works on `spectrum` rows, K-frame means of |X|^2: an RRC-QPSK carrier, a band of noise and an OFDM block of the same
+ * width give crn_measure_device the same record.  A digitally modulated carrier correlates spectral components that lie one symbol rate
+ * apart; stationary noise of any colour does not.  This stage forms that correlation from the per-frame complex spectra, normalised by
+ * the power in both components (a spectral coherence: no calibrated noise power is needed), over every stored segment, and reports the
+ * strongest cell, hence the symbol rate.  It describes detected segments; it is not a detector below the noise (at 0 dB in-band the
+ * feature of a 62-bin segment is lost with 32 frames).
+ * N = fft_len; F = params.frames; X_f[k] is bin k of the complex spectrum of frame f of an epoch: d_frames is [n_epochs][F][N]
+ * interleaved complex fp32, what crn_fft_forward_device writes for n_epochs F consecutive disjoint frames of N samples (the stage does
+ * not care where the array came from).  Per epoch e and slot s < d_epochs[e].n_stored, with lo and width read from d_segments[e][s]:
+ *   1. span      every value read from the records is clamped first: n_stored to 0 .. max_segments, lo to lo mod N (0 .. N - 1), width
+ *                to 0 .. N.  w = min(width, max_width); lo' = (lo + (width - w) div 2) mod N: the central w bins of the segment.
+ *   2. cells     (a, q) for a = a_lo .. a_lo + n_a - 1 and q = 0 .. F - 1.  n_pairs(a) = w - a.  A cell is tested when
+ *                n_pairs(a) >= min_pairs.
+ *   3. pairs     for i = 0 .. n_pairs - 1, with k = (lo' + i) mod N and k' = (lo' + i + a) mod N:
+ *                    C = sum over f of X_f[k'] conj(X_f[k]) e^(-j 2 pi q f / F)        P[k] = sum over f of |X_f[k]|^2
+ *                    rho = |C|^2 / (P[k'] P[k]), and rho = 0 when the product is 0
+ *                in fp32 throughout; the order of the operations is the implementation's (the kernel divides every column by
+ *                sqrt(P) first and takes C from a radix-2 transform over f), so S below is defined to within 8 F 2^-24 absolute of its
+ *                exact value and the same build gives the same bytes.  That holds for spectra of any scale whose P[k] are normal
+ *                fp32 numbers, about 1e-18 <= |X| <= 1e18: P[k'] P[k] and |C|^2 themselves are never formed.
+ *   4. statistic S(a, q) = (sum over i of rho) / n_pairs, the sum in fp64, rounded to fp32 once; 0 <= S <= 1.
+ *                z(a, q) = fl32((F S - 1) sqrt(n_pairs (F + 1) / (F - 1))), formed in fp64 from the fp32 S.  Under white Gaussian noise,
+ *                a rectangular window and disjoint frames rho follows Beta(1, F - 1): z has mean 0 and variance 1.
+ *   5. record    (a, q) = the tested cell of largest z, ties to the smallest a and then the smallest q; n_pairs = n_pairs(a); stat = S
+ *                there; stat_lo and stat_hi = S at (a - 1, q) and (a + 1, q), each 0 where that cell lies outside a_lo .. a_lo + n_a - 1
+ *                or is not tested; n_over = the tested cells with z >= z_min.  With no tested cell the record is all zero bytes, and so
+ *                are the slots at and beyond n_stored: a batch gives the same bytes however it is cut into launches.
+ *   6. profile   d_profile, optional, [n_epochs][max_segments][n_a][F] fp32: S, with 0 for cells not tested and for empty slots.
+ * The feature's cyclic frequency is congruent to q / F modulo one bin and the nearest separation is a: the symbol rate in bins is the
+ * value congruent to q / F that lies nearest a.  A carrier between two separations answers in (a, q) and (a + 1, q), hence the two
+ * neighbour values (crnsense.cyclo_bins interpolates over them).
+ *   Limits       an off-grid CW carrier under the rectangular window gives S ~ 0.99 at q = 0 for every a (its leakage is coherent):
+ *                such segments are recognised by `crest` of crn_measure_device, not here.  The leakage skirt around a strong
+ *                modulated carrier is coherent in the same way: a segment that reaches well into it (80 bins around a 60-bin carrier
+ *                38 dB over the noise) has its largest z at q = 0.  Keep the span to the occupied band, by a detection threshold
+ *                above the skirt or by max_width = the channel's width.  Only the non-conjugate cyclic spectrum is
+ *                formed: the carrier-frequency features of BPSK and MSK are not.  The feature lives where the two shifted copies of
+ *                the pulse overlap, about roll-off x symbol rate bins, so a narrow segment at N = 512 has few pairs.  Disjoint frames
+ *                under the rectangular window leak between adjacent a. */
+typedef struct crn_cyclo_params {
+  int32_t max_segments; /* as given to crn_segments_device: 1 .. 256 */
+  int32_t frames;       /* F: 8, 16, 32 or 64 */
+  int32_t a_lo;         /* the first separation in bins, >= 1 */
+  int32_t n_a;          /* separations: 1 .. 128, a_lo + n_a - 1 <= fft_len / 2 */
+  int32_t max_width;    /* bins of a segment that are looked at, the central ones: 2 .. 1024 */
+  int32_t min_pairs;    /* a cell needs this many pairs: 1 .. max_width */
+  int32_t reserved[2];  /* 0 */
+  float z_min;          /* finite: crn_cyclo_zmin */
+} crn_cyclo_params; /* 36 bytes */
+typedef struct crn_cyclo {
+  int32_t a, q, n_pairs, n_over;
+  float stat, stat_lo, stat_hi, z;
+} crn_cyclo; /* 32 bytes */
+
+/* Enqueue the stage on `stream` over n_epochs epochs, one launch (device pointers, all 16-byte aligned):
+ *   d_frames    [n_epochs][frames][fft_len] complex fp32   the per-frame spectra
+ *   d_epochs    [n_epochs]                                 the headers crn_segments_device wrote (n_stored is read)
+ *   d_segments  [n_epochs][max_segments]                   its records (lo and width are read)
+ *   d_cyclo     [n_epochs][max_segments]                   one record per slot, every slot written
+ *   d_profile   [n_epochs][max_segments][n_a][frames] fp32, or NULL
+ * `h` supplies fft_len and the device, nothing else.  Only enqueues; allocates nothing, keeps no state, needs no workspace.  Whatever
+ * bytes d_epochs and d_segments hold, only the epoch's own frames and records are read and only its own slots written.  Fixed
+ * reduction orders and no floating-point atomics: the same call repeated gives the same bytes.  CRN_ERR_ARG, decided before any device
+ * call, for a NULL h, params, d_frames, d_epochs, d_segments or d_cyclo; n_epochs < 0; any parameter outside the ranges above; a z_min
+ * that is not finite; a nonzero reserved; any of the five arrays not 16-byte aligned.  n_epochs = 0 succeeds and launches nothing. */
+CRN_API int crn_cyclo_device(crn_handle *h, const float *d_frames, int64_t n_epochs, const crn_cyclo_params *params,
+                             const crn_segment_epoch *d_epochs, const crn_segment *d_segments, crn_cyclo *d_cyclo, float *d_profile,
+                             void *stream);
+
+/* z_min for a false-alarm probability pfa per tested cell, host only.  An approximation: the sum of n_pairs Beta(1, F - 1) values is
+ * matched in mean and variance by a Gamma law of shape g = n_pairs (F + 1) / (F - 1), whose upper tail Q(g, g + z sqrt(g)) is inverted
+ * by bisection.  (The rho of neighbouring pairs share a column and the true tail is not Gamma's: in simulated noise the realised rate
+ * at pfa = 1e-2 lay between 0.8 and 1.05 times the nominal one for 23 to 54 pairs.)  Cells of different n_pairs have different thresholds: pass the
+ * smallest n_pairs in use, min_pairs, which is the conservative choice.  CRN_ERR_ARG for pfa outside (0, 1), frames other than 8, 16,
+ * 32 or 64, n_pairs < 1 or a NULL z_min. */
+CRN_API int crn_cyclo_zmin(double pfa, int32_t frames, int32_t n_pairs, double *z_min);
+
 /* -- occupancy map: what every bin did over time -------------------------------------------------------------------------------
  * The occupancy survey of spectrum monitoring (ITU-R SM.2256), per bin: how often each frequency is occupied, how often it changes
  * state and how long it stays busy or idle, the highest and lowest level seen there (max hold, min hold), and the mean level while

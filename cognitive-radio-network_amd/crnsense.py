@@ -55,6 +55,7 @@ EXPORTS = [
     "crn_tcfar_hist_bytes", "crn_tcfar_device",
     "crn_measure_device",
     "crn_occmap_workspace_bytes", "crn_occmap_device",
+    "crn_cyclo_device", "crn_cyclo_zmin",
     "crn_comm_unique_id", "crn_comm_create", "crn_comm_local", "crn_comm_allgather", "crn_comm_gathered",
     "crn_comm_finish", "crn_comm_destroy", "crn_comm_local_addr", "crn_comm_wait", "crn_comm_info",
     "crn_last_error", "crn_abi_version", "crn_build_info",
@@ -255,6 +256,24 @@ OCCMAP_BIN_DTYPE = [("n_epochs", "<i4"), ("n_busy", "<i4"), ("n_rise", "<i4"), (
                     ("run_max", "<i4", (2,)), ("max_hold", "<f4"), ("min_hold", "<f4"), ("reserved", "<i4", (2,)), ("power", "<f8", (2,))]
 OCCMAP_STREAM_DTYPE = [("busy_sum", "<i8"), ("n_epochs", "<i4"), ("usual_bins", "<i4"), ("clear_bins", "<i4"), ("busy_now", "<i4"),
                        ("reserved", "<i4", (2,))]
+
+
+class CycloParams(C.Structure):
+    """crn_cyclo_params (crn_cyclo_device), 36 bytes."""
+    _fields_ = [("max_segments", C.c_int32), ("frames", C.c_int32), ("a_lo", C.c_int32), ("n_a", C.c_int32), ("max_width", C.c_int32),
+                ("min_pairs", C.c_int32), ("reserved", C.c_int32 * 2), ("z_min", C.c_float)]
+
+
+class Cyclo(C.Structure):
+    """crn_cyclo: one slot's record, 32 bytes."""
+    _fields_ = [("a", C.c_int32), ("q", C.c_int32), ("n_pairs", C.c_int32), ("n_over", C.c_int32), ("stat", C.c_float), ("stat_lo", C.c_float),
+                ("stat_hi", C.c_float), ("z", C.c_float)]
+
+
+# numpy view of the records crn_cyclo_device writes: np.frombuffer(bytes, CYCLO_DTYPE).reshape(n_epochs, max_segments), slot by slot next
+# to SEGMENT_DTYPE's
+CYCLO_DTYPE = [("a", "<i4"), ("q", "<i4"), ("n_pairs", "<i4"), ("n_over", "<i4"), ("stat", "<f4"), ("stat_lo", "<f4"), ("stat_hi", "<f4"),
+               ("z", "<f4")]
 CFAR_METHODS = {"ca": CFAR_CA, "go": CFAR_GO, "so": CFAR_SO, "os": CFAR_OS}
 
 
@@ -398,6 +417,9 @@ def lib():
         L.crn_occmap_workspace_bytes.argtypes, L.crn_occmap_workspace_bytes.restype = [C.c_int64, C.POINTER(OccmapParams)], C.c_int64
         L.crn_occmap_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(OccmapParams), C.c_void_p, C.c_void_p, C.c_void_p,
                                         C.c_void_p, C.c_int64, C.c_void_p]
+        L.crn_cyclo_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(CycloParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.c_void_p]
+        L.crn_cyclo_zmin.argtypes = [C.c_double, C.c_int32, C.c_int32, C.POINTER(C.c_double)]
         L.crn_ingest_create.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]
         L.crn_ingest_push.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
         L.crn_ingest_flush.argtypes = [C.c_void_p]
@@ -714,6 +736,42 @@ def floor_db(records, fallback=None):
     out = np.full(m.shape, np.nan if fallback is None else float(fallback), np.float64)
     np.log10(m, out=out, where=m > 0)
     return np.where(m > 0, 10.0 * out, out)
+
+
+def cyclo_zmin(pfa, frames, n_pairs):
+    """z_min of crn_cyclo_params at which a tested cell of n_pairs pairs exceeds it in noise with probability pfa (crn_cyclo_zmin; a
+    Gamma approximation).  Pass the smallest n_pairs in use, min_pairs: the conservative choice."""
+    z = C.c_double()
+    check(lib().crn_cyclo_zmin(float(pfa), int(frames), int(n_pairs), C.byref(z)), "crn_cyclo_zmin")
+    return z.value
+
+
+def cyclo_params(max_segments=16, frames=32, a_lo=8, n_a=64, max_width=256, min_pairs=16, z_min=None, pfa=1e-6):
+    """crn_cyclo_params: max_segments as given to the segment stage, frames the frames of an epoch in the array of spectra; separations
+    a_lo .. a_lo + n_a - 1 bins over the central max_width bins of a segment, a cell tested from min_pairs pairs on; z_min as given or
+    cyclo_zmin(pfa, frames, min_pairs)."""
+    z = cyclo_zmin(pfa, frames, min_pairs) if z_min is None else z_min
+    return CycloParams(max_segments=int(max_segments), frames=int(frames), a_lo=int(a_lo), n_a=int(n_a), max_width=int(max_width),
+                       min_pairs=int(min_pairs), z_min=float(z))
+
+
+def cyclo_bins(rec, frames):
+    """The symbol rate in bins from a record of crn_cyclo_device (a CYCLO_DTYPE element, a Cyclo, or anything with those fields by name
+    or key): the peak in a is interpolated over its two neighbours, a^ = a + (stat_hi - stat_lo) / (stat_lo + stat + stat_hi), and the
+    value congruent to q / frames modulo one bin that lies nearest a^ is returned.  0.0 for a record with no tested cell."""
+    get = (lambda k: getattr(rec, k)) if hasattr(rec, "stat") else (lambda k: rec[k])
+    a, q, s0, s1, s2 = int(get("a")), int(get("q")), float(get("stat_lo")), float(get("stat")), float(get("stat_hi"))
+    if int(get("n_pairs")) <= 0:
+        return 0.0
+    total = s0 + s1 + s2
+    a_hat = a + ((s2 - s0) / total if total > 0.0 else 0.0)
+    frac = q / float(frames)
+    return float(round(a_hat - frac)) + frac
+
+
+def cyclo_hz(rec, frames, fft_len, fs):
+    """The symbol rate in Hz: cyclo_bins x fs / fft_len."""
+    return cyclo_bins(rec, frames) * float(fs) / float(fft_len)
 
 
 def hole_hz(lo, width, fft_len, fs, fc):
@@ -1067,6 +1125,15 @@ class Sensor:
         v = lambda ptr: C.c_void_p(ptr or None)      # noqa: E731
         check(lib().crn_occmap_device(self._h, v(mask_ptr), v(spectrum_ptr), n_epochs, C.byref(q), v(bins_ptr), v(streams_ptr), v(usual_mask_ptr),
                                       v(workspace_ptr), int(workspace_bytes), v(stream)), "crn_occmap_device")
+
+    def cyclo_device(self, frames_ptr, n_epochs, params, epochs_ptr, segments_ptr, cyclo_ptr, profile_ptr=0, stream=0):
+        """The strongest cyclic feature of every stored segment of n_epochs epochs (device pointers; params from cyclo_params): frames_ptr
+        [n_epochs][params.frames][fft_len] complex float32, what fft_forward_device writes for the epochs' frames; epochs_ptr and
+        segments_ptr what segments_device wrote with the same max_segments; cyclo_ptr [n_epochs][max_segments] CYCLO_DTYPE, every slot
+        written; profile_ptr [n_epochs][max_segments][n_a][frames] float32 or 0.  Only enqueues."""
+        v = lambda ptr: C.c_void_p(ptr or None)      # noqa: E731
+        check(lib().crn_cyclo_device(self._h, v(frames_ptr), n_epochs, C.byref(params), v(epochs_ptr), v(segments_ptr), v(cyclo_ptr),
+                                     v(profile_ptr), v(stream)), "crn_cyclo_device")
 
     def fuse_device(self, mask_ptr, spectrum_ptr, n_epochs, params, fused_mask_ptr=0, fused_spectrum_ptr=0, rows_ptr=0, stream=0):
         """Fuses groups of params.group_size streams (fuse_params; device pointers): mask_ptr [n_epochs][fft_len / 32] uint32 and

@@ -264,3 +264,22 @@ int crn_lad_factor(double pfa, int32_t frames_per_epoch, double t_cme, double *f
   *factor = q / K / m;
   return CRN_OK;
 }
+
+int crn_cyclo_zmin(double pfa, int32_t frames, int32_t n_pairs, double *z_min) {
+  if (!z_min) return crn::fail(CRN_ERR_ARG, "crn_cyclo_zmin: null z_min");
+  if (!(pfa > 0.0 && pfa < 1.0)) return crn::fail(CRN_ERR_ARG, "crn_cyclo_zmin: pfa must be in (0, 1)");
+  if (frames != 8 && frames != 16 && frames != 32 && frames != 64) return crn::fail(CRN_ERR_ARG, "crn_cyclo_zmin: frames must be 8, 16, 32 or 64");
+  if (n_pairs < 1) return crn::fail(CRN_ERR_ARG, "crn_cyclo_zmin: n_pairs < 1");
+  // sum of n Beta(1, F - 1): mean n / F, variance n (F - 1) / (F^2 (F + 1)); the Gamma law of that mean and variance has shape
+  // g = n (F + 1) / (F - 1), and in its unit scale the sum is x = g + z sqrt(g)
+  const double F = frames, g = n_pairs * (F + 1.0) / (F - 1.0), lg = std::lgamma(g);
+  double x = 0.0;
+  auto tail = [&](double s) {
+    double P, Q;
+    inc_gamma(g, s, lg, &P, &Q);
+    return Q;
+  };
+  if (!solve_alpha(tail, pfa, &x)) return crn::fail(CRN_ERR_ARG, "crn_cyclo_zmin: pfa too small");
+  *z_min = (x - g) / std::sqrt(g);
+  return CRN_OK;
+}
