@@ -1007,6 +1007,73 @@ CRN_API int crn_occmap_device(crn_handle *h, const uint32_t *d_bin_mask, const f
                               const crn_occmap_params *params, crn_occmap_bin *d_bins, crn_occmap_stream *d_streams,
                               uint32_t *d_usual_mask, void *d_workspace, int64_t workspace_bytes, void *stream);
 
+/* -- hops: how the channels move together -----------------------------------------------------------------------------------------
+ * crn_channels_device keeps one two-state record per channel, each channel on its own.  A primary user that hops between channels (the
+ * reference's CE_Random_Behaviour_PU and CE_PU_MARKOV_Chain_Tx, the interferer's TX_FREQ_BEHAVIOR_SWEEP) is one emitter whose next
+ * channel depends on the one it is on: this stage counts, per stream, which channel was busy d epochs after which, for up to 8 lags d,
+ * and the moves from one channel to another.  Its input is d_busy of crn_channels_device, one 64-bit busy word per epoch.  A batch is
+ * laid out as for crn_channels_device: n_epochs / epochs_per_stream streams of epochs_per_stream consecutive epochs in time order.
+ *   States     C = n_channels, 1..63.  The augmented word of an epoch is a = w & ((1 << C) - 1), and a = 1 << 63 when that is 0: index 63
+ *              is the virtual channel "nothing busy", bits C..62 are never set, and the bits of d_busy at or above C, bit 63 included,
+ *              are ignored.
+ *   Lags       n_lags in 1..8, lag[m] strictly ascending, each in 1..64.
+ *   Record     one per stream, in the caller's device memory, its own carry from call to call, 64 + 512 + 16384 + n_lags * 16896 bytes:
+ *                int64 n_epochs (epochs seen so far); int32 n_channels, n_lags, lag[8] (unused entries 0), reserved[4] (0)   64 bytes
+ *                uint64 hist[64]    bit k of hist[c] = bit c of the augmented word of epoch n_epochs - 1 - k, for k < min(n_epochs, 64);
+ *                                   every other bit is 0
+ *                int32 hop[64][64]
+ *                per lag m: int32 from[64], to[64], pair[64][64]
+ *   Rule       sequential, and the definition.  Per epoch, T = the stream's n_epochs before it, cur = its augmented word:
+ *                for each lag m with T >= lag[m]:  prev = the augmented word of epoch T - lag[m] (from hist)
+ *                    from[m][i] += 1 for every set bit i of prev;  to[m][j] += 1 for every set bit j of cur
+ *                    pair[m][i][j] += 1 for every such i and j
+ *                if T >= 1:  prev = the word of epoch T - 1;  fall = prev & ~cur;  rise = cur & ~prev
+ *                    hop[i][j] += 1 for every i in fall and j in rise          (the moves; stays are left out)
+ *                cur is shifted into hist;  n_epochs += 1
+ *              Every int32 count saturates at 2^31 - 1.
+ *   Carry      the record is taken as empty (all zero) when first != 0, when its n_epochs <= 0, or when its n_channels, n_lags or any
+ *              lag[] differs from the call's (the call's lag[] entries at and above n_lags are not looked at and count as 0).  On
+ *              reading, hist words are masked to k < min(n_epochs, 64) and to the channel positions c < C and c = 63, and a negative
+ *              count is read as 0.  No index is ever read from a record, so a foreign buffer cannot cause an access outside the buffers.
+ *   Cut independence   a stream given in one call and the same stream cut into several calls (first = 1, then 0) give identical bytes:
+ *              everything is an integer, and saturating sums of non-negative terms do not depend on the order. */
+typedef struct crn_hop_params {
+  int32_t n_channels;        /* 1..63 */
+  int32_t epochs_per_stream; /* >= 1, divides n_epochs */
+  int32_t n_lags;            /* 1..8 */
+  int32_t first;             /* != 0: the records' contents mean nothing, start afresh */
+  int32_t lag[8];            /* lag[0 .. n_lags - 1] strictly ascending, each in 1..64 */
+  int32_t reserved[4];       /* 0 */
+} crn_hop_params; /* 64 bytes */
+
+/* Bytes of n_streams records, and bytes of device scratch crn_hops_device needs for n_epochs epochs, under `params`: neither needs a
+ * handle or a device.  -1 for a NULL params, a negative count, n_channels outside 1..63, n_lags outside 1..8, a lag outside 1..64 or
+ * not above the one before it, epochs_per_stream < 1 (for the workspace: or not dividing n_epochs), or a nonzero reserved field;
+ * otherwise the size (the workspace's is positive for n_epochs = 0 too). */
+CRN_API int64_t crn_hops_bytes(int64_t n_streams, const crn_hop_params *params);
+CRN_API int64_t crn_hops_workspace_bytes(int64_t n_epochs, const crn_hop_params *params);
+
+/* Enqueue the stage on `stream`, two launches (device pointers):
+ *   d_busy       [n_epochs] uint64                  one busy word per epoch (8-byte aligned)
+ *   d_records    record_bytes >= crn_hops_bytes of the batch's streams (16-byte aligned): read (unless first != 0), then rewritten
+ *   d_workspace  workspace_bytes >= crn_hops_workspace_bytes of scratch (8-byte aligned); its contents before and after mean nothing
+ * `h` supplies the device and nothing else: the words may come from crn_channels_device, from the same stage run after
+ * crn_fuse_device or on a mask of crn_lad_device, or from anywhere else.  Only enqueues, allocates nothing, keeps no host state; the
+ * same call gives the same bytes.  CRN_ERR_ARG, decided before any device call, for a NULL h, params, d_busy, d_records or d_workspace;
+ * n_epochs < 0; everything crn_hops_workspace_bytes refuses; a misaligned pointer; records or a workspace too small.  n_epochs = 0
+ * succeeds and launches nothing, with first != 0 too (the records are then left as they are). */
+CRN_API int crn_hops_device(crn_handle *h, const uint64_t *d_busy, int64_t n_epochs, const crn_hop_params *params, void *d_records,
+                            int64_t record_bytes, void *d_workspace, int64_t workspace_bytes, void *stream);
+
+/* Where the emitters seen now will be lag[m] epochs on, host only (`record` is a host copy of ONE record; `word` the busy word of the
+ * epoch at hand, a its augmented word):
+ *   p[j] = the largest, over the set bits i of a, of (pair[m][i][j] + prior) / (from[m][i] + 2 prior); a 0 / 0 gives 0.5
+ *   p[j] = 0 for C <= j < 63; p[63] is the probability that nothing is busy lag[m] epochs on
+ * With several emitters on the air a channel is taken to be as threatened as the most threatening of them makes it: that is the rule,
+ * not an approximation of a joint model.  prior = 1 is Laplace's rule, 0 the plain frequencies.  CRN_ERR_ARG for a NULL pointer, m
+ * outside 0 .. n_lags - 1, a negative or non-finite prior, or a head whose n_channels or n_lags is out of range. */
+CRN_API int crn_hop_forecast(const void *record, int32_t m, uint64_t word, double prior, double p[64]);
+
 /* Allocate, now, the device scratch and pinned staging that crn_sense_run_host needs for up to
  * max_epochs dense epochs of full-length frames (and their per-bin spectra when want_spectrum != 0),
  * and load the kernels: a later crn_sense_run_host within that size allocates nothing.  An engine

@@ -56,6 +56,7 @@ EXPORTS = [
     "crn_measure_device",
     "crn_occmap_workspace_bytes", "crn_occmap_device",
     "crn_cyclo_device", "crn_cyclo_zmin",
+    "crn_hops_bytes", "crn_hops_workspace_bytes", "crn_hops_device", "crn_hop_forecast",
     "crn_comm_unique_id", "crn_comm_create", "crn_comm_local", "crn_comm_allgather", "crn_comm_gathered",
     "crn_comm_finish", "crn_comm_destroy", "crn_comm_local_addr", "crn_comm_wait", "crn_comm_info",
     "crn_last_error", "crn_abi_version", "crn_build_info",
@@ -274,6 +275,25 @@ class Cyclo(C.Structure):
 # to SEGMENT_DTYPE's
 CYCLO_DTYPE = [("a", "<i4"), ("q", "<i4"), ("n_pairs", "<i4"), ("n_over", "<i4"), ("stat", "<f4"), ("stat_lo", "<f4"), ("stat_hi", "<f4"),
                ("z", "<f4")]
+
+
+class HopParams(C.Structure):
+    """crn_hop_params (crn_hops_device), 64 bytes."""
+    _fields_ = [("n_channels", C.c_int32), ("epochs_per_stream", C.c_int32), ("n_lags", C.c_int32), ("first", C.c_int32), ("lag", C.c_int32 * 8),
+                ("reserved", C.c_int32 * 4)]
+
+
+# numpy view of ONE record crn_hops_device keeps, for n_lags lags: np.frombuffer(bytes, hop_dtype(n_lags)); hop_record does it
+CRN_HOP_IDLE = 63                             # the virtual channel "nothing busy"
+
+
+def hop_dtype(n_lags):
+    import numpy as np
+    return np.dtype([("n_epochs", "<i8"), ("n_channels", "<i4"), ("n_lags", "<i4"), ("lag", "<i4", (8,)), ("reserved", "<i4", (4,)),
+                     ("hist", "<u8", (64,)), ("hop", "<i4", (64, 64)),
+                     ("lags", [("from", "<i4", (64,)), ("to", "<i4", (64,)), ("pair", "<i4", (64, 64))], (int(n_lags),))])
+
+
 CFAR_METHODS = {"ca": CFAR_CA, "go": CFAR_GO, "so": CFAR_SO, "os": CFAR_OS}
 
 
@@ -420,6 +440,10 @@ def lib():
         L.crn_cyclo_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(CycloParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.c_void_p]
         L.crn_cyclo_zmin.argtypes = [C.c_double, C.c_int32, C.c_int32, C.POINTER(C.c_double)]
+        for f in (L.crn_hops_bytes, L.crn_hops_workspace_bytes):
+            f.argtypes, f.restype = [C.c_int64, C.POINTER(HopParams)], C.c_int64
+        L.crn_hops_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(HopParams), C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]
+        L.crn_hop_forecast.argtypes = [C.c_void_p, C.c_int32, C.c_uint64, C.c_double, C.POINTER(C.c_double)]
         L.crn_ingest_create.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]
         L.crn_ingest_push.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
         L.crn_ingest_flush.argtypes = [C.c_void_p]
@@ -774,6 +798,86 @@ def cyclo_hz(rec, frames, fft_len, fs):
     return cyclo_bins(rec, frames) * float(fs) / float(fft_len)
 
 
+def hop_params(n_channels, epochs_per_stream, lags=(1,), first=False):
+    """crn_hop_params: `lags` strictly ascending, each in 1..64, at most 8 of them."""
+    lags = [int(d) for d in lags]
+    if len(lags) > 8:
+        raise ValueError(f"at most 8 lags, not {len(lags)}")
+    q = HopParams(n_channels=int(n_channels), epochs_per_stream=int(epochs_per_stream), n_lags=len(lags), first=int(bool(first)))
+    for m, d in enumerate(lags):
+        q.lag[m] = d
+    return q
+
+
+def hops_bytes(n_streams, n_channels, lags=(1,)):
+    """Bytes of n_streams records of Sensor.hops_device (crn_hops_bytes): no handle, no device."""
+    q = hop_params(n_channels, 1, lags)
+    nb = lib().crn_hops_bytes(int(n_streams), C.byref(q))
+    if nb < 0:
+        raise CrnError(f"crn_hops_bytes: arguments out of range ({nb})")
+    return nb
+
+
+def hops_workspace_bytes(n_epochs, n_channels, epochs_per_stream=None, lags=(1,)):
+    """Bytes of device scratch Sensor.hops_device needs (crn_hops_workspace_bytes): no handle, no device."""
+    q = hop_params(n_channels, n_epochs if epochs_per_stream is None else epochs_per_stream, lags)
+    nb = lib().crn_hops_workspace_bytes(int(n_epochs), C.byref(q))
+    if nb <= 0:
+        raise CrnError(f"crn_hops_workspace_bytes: arguments out of range ({nb})")
+    return nb
+
+
+def hop_record(buf, n_lags):
+    """One record of crn_hops_device as numpy views of `buf` (bytes, or a uint8 array, of exactly one record of n_lags lags): a dict
+    with n_epochs, n_channels, n_lags, lag [8], hist [64] uint64, hop [64][64], and from [n_lags][64], to [n_lags][64], pair
+    [n_lags][64][64]; "raw" is the record itself, what hop_forecast hands to the library."""
+    import numpy as np
+    dt = hop_dtype(n_lags)
+    raw = np.frombuffer(buf, np.uint8) if isinstance(buf, (bytes, bytearray, memoryview)) else np.ascontiguousarray(buf).view(np.uint8).reshape(-1)
+    if raw.size != dt.itemsize:
+        raise ValueError(f"hop_record takes ONE record of {dt.itemsize} bytes for {n_lags} lags, not {raw.size}")
+    r = raw.view(dt)[0]
+    return {"raw": raw, "n_epochs": r["n_epochs"], "n_channels": r["n_channels"], "n_lags": r["n_lags"], "lag": r["lag"], "hist": r["hist"],
+            "hop": r["hop"], "from": r["lags"]["from"], "to": r["lags"]["to"], "pair": r["lags"]["pair"]}
+
+
+def hop_forecast(rec, m, word, prior=1.0):
+    """p [64] of crn_hop_forecast: how likely channel j is busy lag[m] epochs after an epoch whose busy word is `word` (p[63]: nothing
+    busy), on one record as hop_record returns it (or its bytes)."""
+    import numpy as np
+    raw = rec["raw"] if isinstance(rec, dict) else np.frombuffer(rec, np.uint8)
+    raw = np.ascontiguousarray(raw)
+    p = (C.c_double * 64)()
+    check(lib().crn_hop_forecast(raw.ctypes.data_as(C.c_void_p), int(m), int(word) & (2 ** 64 - 1), float(prior), p), "crn_hop_forecast")
+    return np.array(p[:], np.float64)
+
+
+def hop_table(rec, prior=0.0):
+    """The jump chain of one record: [C + 1][C + 1], row i = hop[i][j] / sum_j hop[i][j] over the channels 0 .. C - 1 and, last, the idle
+    state (`prior` added to every off-diagonal cell; a row never left is all zero).  With a primary user that dwells many epochs on a
+    channel this is its transition table without the diagonal, rows renormalised."""
+    import numpy as np
+    nch = int(rec["n_channels"])
+    idx = list(range(nch)) + [CRN_HOP_IDLE]
+    h = np.maximum(np.asarray(rec["hop"], np.float64)[np.ix_(idx, idx)], 0.0) + float(prior) * (1.0 - np.eye(nch + 1))
+    tot = h.sum(axis=1, keepdims=True)
+    return np.divide(h, tot, out=np.zeros_like(h), where=tot > 0)
+
+
+def next_channel(rec, word, horizon, prior=1.0):
+    """The channel j < C least likely to be hit in the next `horizon` epochs given the busy word of the epoch at hand: the largest
+    prod over d = 1 .. horizon of (1 - p_d[j]), p_d = hop_forecast at lag d; ties go to the lowest j.  ValueError unless the lags
+    1 .. horizon are all in the record."""
+    import numpy as np
+    lags = [int(d) for d in rec["lag"][:int(rec["n_lags"])]]
+    if horizon < 1 or any(d not in lags for d in range(1, horizon + 1)):
+        raise ValueError(f"next_channel: the record keeps the lags {lags}, not all of 1 .. {horizon}")
+    free = np.ones(64)
+    for d in range(1, horizon + 1):
+        free *= 1.0 - hop_forecast(rec, lags.index(d), word, prior)
+    return int(np.argmax(free[:int(rec["n_channels"])]))
+
+
 def hole_hz(lo, width, fft_len, fs, fc):
     """(centre frequency, bandwidth) in Hz of a hole from crn_holes_device: the centre is the geometric one, at bin lo + (width - 1) / 2,
     and the mapping of bins to hertz is segment_hz's, so a hole that crosses the wrap (lo + width > N) comes out around fc."""
@@ -1125,6 +1229,15 @@ class Sensor:
         v = lambda ptr: C.c_void_p(ptr or None)      # noqa: E731
         check(lib().crn_occmap_device(self._h, v(mask_ptr), v(spectrum_ptr), n_epochs, C.byref(q), v(bins_ptr), v(streams_ptr), v(usual_mask_ptr),
                                       v(workspace_ptr), int(workspace_bytes), v(stream)), "crn_occmap_device")
+
+    def hops_device(self, busy_ptr, n_epochs, params, records_ptr, record_bytes, workspace_ptr, workspace_bytes, stream=None):
+        """Channel-to-channel transition counts from n_epochs busy words (device pointers; params from hop_params): busy_ptr [n_epochs]
+        uint64 as channels_device writes them; records_ptr hops_bytes(...) of records, one per stream (hop_record), read unless
+        params.first and then rewritten; workspace_ptr at least hops_workspace_bytes(...) of scratch.  n_streams = n_epochs /
+        params.epochs_per_stream.  Only enqueues."""
+        v = lambda ptr: C.c_void_p(ptr or None)      # noqa: E731
+        check(lib().crn_hops_device(self._h, v(busy_ptr), n_epochs, C.byref(params), v(records_ptr), int(record_bytes), v(workspace_ptr),
+                                    int(workspace_bytes), v(stream)), "crn_hops_device")
 
     def cyclo_device(self, frames_ptr, n_epochs, params, epochs_ptr, segments_ptr, cyclo_ptr, profile_ptr=0, stream=0):
         """The strongest cyclic feature of every stored segment of n_epochs epochs (device pointers; params from cyclo_params): frames_ptr
