@@ -1074,6 +1074,63 @@ CRN_API int crn_hops_device(crn_handle *h, const uint64_t *d_busy, int64_t n_epo
  * outside 0 .. n_lags - 1, a negative or non-finite prior, or a head whose n_channels or n_lags is out of range. */
 CRN_API int crn_hop_forecast(const void *record, int32_t m, uint64_t word, double prior, double p[64]);
 
+/* -- extraction: a detected emitter as a baseband sample stream -------------------------------------------------------------------
+ * The stages above find an emitter, follow it and describe it; this one hands out its samples, mixed to baseband, band-limited and
+ * decimated, without the raw IQ leaving the device: an overlap-save (fast-convolution) channelizer on per-frame spectra.
+ * N = fft_len.  d_spectra is [n_frames][N] interleaved complex fp32, what crn_fft_forward_device writes for samples_per_frame = N and
+ * frame_stride = N / 2 (half-overlapped frames under no window; the stage cannot check that, it is the caller's contract).  n_frames
+ * = S F: S streams of F = frames_per_stream consecutive frames each.  M = out_len, one of 16, 32, 64, 128, 256, M <= N / 2.  A channel
+ * is a 16-byte record in device memory, so that a later stage can write it; kappa = centre mod N, taken into 0 .. N - 1 (also for
+ * negative and extreme values).  d_taper[M] is fp32; entry j weights offset i = j - M / 2, so i runs over -M / 2 .. M / 2 - 1.  Per
+ * channel c and frame t = 0 .. F - 1 of its stream, X_t that frame's spectrum and H the taper:
+ *   1. taper     Z[i] = (fl32(Re X_t[(kappa + i) mod N] H[i]), fl32(Im X_t[(kappa + i) mod N] H[i]))
+ *   2. block     y[n] = (1 / N) sum over i of Z[i] e^(+j 2 pi i n / M) for n = M / 4 .. 3 M / 4 - 1, the middle half of the block.  1 / N
+ *                is a power of two: a tone of amplitude A on bin kappa comes out with amplitude A H[0].
+ *   3. sign      y is negated when kappa (t0 + t) is odd: a hop of N / 2 samples turns the mixer e^(-j 2 pi kappa m / N) by e^(-j pi kappa).
+ *                t0 is the index within the stream of the call's first frame; only its parity matters.
+ *   4. row       d_out[c][t M / 2 + (n - M / 4)] = y[n], interleaved complex fp32; a row holds F M / 2 samples.
+ *   5. timing    the output rate is M / N of the input rate; output sample u of a stream (counted from t0 = 0) sits at input sample
+ *                (u + M / 4) N / M of the stream.  The first N / 4 input samples of a stream have no output, nor have the last N / 4 of
+ *                its last frame.
+ *   6. no stream a channel whose `stream` is outside 0 .. S - 1 gets a row of zero bytes.
+ *   7. safety    whatever bytes d_channels holds, only rows of d_spectra inside the batch are read and only the channel's own row written.
+ *   8. no state  there is no carry: a stream cut into calls, with t0 advanced by the frames already given, yields the same bytes as one
+ *                call, and a call repeated yields the same bytes.
+ * Exactness: step 1 is exact as written.  Step 2 is an fp32 radix-2 transform whose order is the implementation's; with u = 2^-24 every
+ * sample is within gamma u (sum over i of |Z[i]|) / N of the exact value, gamma = 5 log2(M) + 4 (44 at M = 256): log2(M) butterfly
+ * levels, each a rounded difference (u) and a product with a rounded factor ((1 + sqrt 2) u for the product, u / sqrt 2 for the
+ * factor), rounded up to 5 u a level, and one more such product between the two passes.  The scale and the sign are exact.  A taper
+ * of zeros gives zeros (of either sign).
+ *   Limits       the taper's roll-off is the filter: what lies within its flat part comes out unchanged, what lies in the roll-off is
+ *                weighted, and the time response of the roll-off must have died within N / 4 samples for the blocks to join.  With
+ *                N = 1024, M = 64 and a flat part of +-16 bins an off-grid tone joins over 39 borders within 2.7e-4 of its amplitude;
+ *                N = 4096, M = 256, flat +-96: 1.3e-5; N = 512, M = 16, flat +-4, a roll-off of 4 bins: 1.8e-2.  Choose M so that the
+ *                roll-off has 16 bins or more.  All channels of a call share M and the taper.  No resampling to a symbol rate. */
+typedef struct crn_extract_params {
+  int32_t out_len;           /* M: 16, 32, 64, 128 or 256, and <= fft_len / 2 */
+  int32_t frames_per_stream; /* F >= 1, divides n_frames */
+  int32_t t0;                /* >= 0: frames of each stream given to earlier calls */
+  int32_t reserved[5];       /* 0 */
+} crn_extract_params; /* 32 bytes */
+typedef struct crn_extract_channel {
+  int32_t stream;            /* 0 .. S - 1; anything else: a row of zeros */
+  int32_t centre;            /* bin; taken mod fft_len */
+  int32_t reserved[2];       /* not looked at */
+} crn_extract_channel; /* 16 bytes */
+
+/* Enqueue the stage on `stream`, one launch (device pointers, all 16-byte aligned):
+ *   d_spectra   [n_frames][fft_len] complex fp32              the spectra of half-overlapped frames
+ *   d_channels  [n_chan]                                      the channel records
+ *   d_taper     [out_len] fp32                                H
+ *   d_out       [n_chan][frames_per_stream out_len / 2] complex fp32, every sample written
+ * `h` supplies fft_len and the device, nothing else.  Only enqueues; allocates nothing, keeps no state, needs no workspace.  No atomics:
+ * the same call repeated gives the same bytes.  CRN_ERR_ARG, decided before any device call, for a NULL h, params, d_spectra,
+ * d_channels, d_taper or d_out; an out_len not in the list or above fft_len / 2; frames_per_stream < 1 or not dividing n_frames;
+ * t0 < 0; n_chan outside 0 .. 65536; n_frames < 0; a nonzero reserved in params; any of the four arrays not 16-byte aligned.
+ * n_frames = 0 or n_chan = 0 succeeds and launches nothing. */
+CRN_API int crn_extract_device(crn_handle *h, const float *d_spectra, int64_t n_frames, const crn_extract_params *params,
+                               const crn_extract_channel *d_channels, int32_t n_chan, const float *d_taper, float *d_out, void *stream);
+
 /* Allocate, now, the device scratch and pinned staging that crn_sense_run_host needs for up to
  * max_epochs dense epochs of full-length frames (and their per-bin spectra when want_spectrum != 0),
  * and load the kernels: a later crn_sense_run_host within that size allocates nothing.  An engine

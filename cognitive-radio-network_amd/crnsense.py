@@ -57,6 +57,7 @@ EXPORTS = [
     "crn_occmap_workspace_bytes", "crn_occmap_device",
     "crn_cyclo_device", "crn_cyclo_zmin",
     "crn_hops_bytes", "crn_hops_workspace_bytes", "crn_hops_device", "crn_hop_forecast",
+    "crn_extract_device",
     "crn_comm_unique_id", "crn_comm_create", "crn_comm_local", "crn_comm_allgather", "crn_comm_gathered",
     "crn_comm_finish", "crn_comm_destroy", "crn_comm_local_addr", "crn_comm_wait", "crn_comm_info",
     "crn_last_error", "crn_abi_version", "crn_build_info",
@@ -294,6 +295,21 @@ def hop_dtype(n_lags):
                      ("lags", [("from", "<i4", (64,)), ("to", "<i4", (64,)), ("pair", "<i4", (64, 64))], (int(n_lags),))])
 
 
+class ExtractParams(C.Structure):
+    """crn_extract_params (crn_extract_device), 32 bytes."""
+    _fields_ = [("out_len", C.c_int32), ("frames_per_stream", C.c_int32), ("t0", C.c_int32), ("reserved", C.c_int32 * 5)]
+
+
+class ExtractChannel(C.Structure):
+    """crn_extract_channel: one channel of crn_extract_device, 16 bytes."""
+    _fields_ = [("stream", C.c_int32), ("centre", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
+# numpy view of the channel records crn_extract_device reads: np.zeros(n_chan, EXTRACT_CHANNEL_DTYPE); extract_channels fills one
+EXTRACT_CHANNEL_DTYPE = [("stream", "<i4"), ("centre", "<i4"), ("reserved", "<i4", (2,))]
+EXTRACT_OUT_LENS = (16, 32, 64, 128, 256)
+
+
 CFAR_METHODS = {"ca": CFAR_CA, "go": CFAR_GO, "so": CFAR_SO, "os": CFAR_OS}
 
 
@@ -444,6 +460,8 @@ def lib():
             f.argtypes, f.restype = [C.c_int64, C.POINTER(HopParams)], C.c_int64
         L.crn_hops_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(HopParams), C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]
         L.crn_hop_forecast.argtypes = [C.c_void_p, C.c_int32, C.c_uint64, C.c_double, C.POINTER(C.c_double)]
+        L.crn_extract_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(ExtractParams), C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
+                                         C.c_void_p]
         L.crn_ingest_create.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]
         L.crn_ingest_push.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
         L.crn_ingest_flush.argtypes = [C.c_void_p]
@@ -796,6 +814,51 @@ def cyclo_bins(rec, frames):
 def cyclo_hz(rec, frames, fft_len, fs):
     """The symbol rate in Hz: cyclo_bins x fs / fft_len."""
     return cyclo_bins(rec, frames) * float(fs) / float(fft_len)
+
+
+def extract_params(out_len, frames_per_stream, t0=0):
+    """crn_extract_params: out_len = M samples of a block, of which M / 2 are kept per frame; frames_per_stream = F; t0 = the frames of
+    each stream that earlier calls were given."""
+    return ExtractParams(out_len=int(out_len), frames_per_stream=int(frames_per_stream), t0=int(t0))
+
+
+def extract_taper(out_len, flat):
+    """The taper H of crn_extract_device as float32 [out_len], entry j for offset i = j - M / 2: 1 for |i| <= flat, a raised-cosine
+    roll-off 0.5 (1 + cos(pi (|i| - flat) / (M / 2 - flat))) beyond, which reaches 0 at i = -M / 2.  Computed in float64 and rounded once."""
+    import numpy as np
+    m, flat = int(out_len), int(flat)
+    if m not in EXTRACT_OUT_LENS or not 0 <= flat < m // 2:
+        raise ValueError(f"extract_taper: out_len must be one of {EXTRACT_OUT_LENS} and 0 <= flat < out_len / 2, not {out_len}, {flat}")
+    i = np.abs(np.arange(m, dtype=np.float64) - m // 2)
+    h = np.where(i <= flat, 1.0, 0.5 * (1.0 + np.cos(np.pi * (i - flat) / (m // 2 - flat))))
+    h[0] = 0.0
+    return h.astype(np.float32)
+
+
+def extract_channels(records, stream=0, fft_len=None):
+    """Channel records (EXTRACT_CHANNEL_DTYPE) for the emitters of ONE stream: `records` are that stream's track records (TRACK_DTYPE: the
+    rounded `centre`), or segment records of one of its epochs (SEGMENT_DTYPE: lo + the rounded `centroid`), or plain bin numbers;
+    `stream` is carried into every record.  With fft_len the centres are taken into 0 .. fft_len - 1 (the stage does so itself)."""
+    import numpy as np
+    r = np.asarray(records)
+    names = r.dtype.names or ()
+    if "centre" in names:
+        centre = np.rint(r["centre"].astype(np.float64))
+    elif "centroid" in names:
+        centre = r["lo"].astype(np.float64) + np.rint(r["centroid"].astype(np.float64))
+    else:
+        centre = np.rint(r.astype(np.float64))
+    centre = centre.reshape(-1).astype(np.int64)
+    if fft_len is not None:
+        centre %= int(fft_len)
+    out = np.zeros(centre.size, np.dtype(EXTRACT_CHANNEL_DTYPE))
+    out["stream"], out["centre"] = int(stream), centre
+    return out
+
+
+def extract_rate(fs, fft_len, out_len):
+    """Sample rate of the streams crn_extract_device writes: fs out_len / fft_len."""
+    return float(fs) * int(out_len) / int(fft_len)
 
 
 def hop_params(n_channels, epochs_per_stream, lags=(1,), first=False):
@@ -1238,6 +1301,15 @@ class Sensor:
         v = lambda ptr: C.c_void_p(ptr or None)      # noqa: E731
         check(lib().crn_hops_device(self._h, v(busy_ptr), n_epochs, C.byref(params), v(records_ptr), int(record_bytes), v(workspace_ptr),
                                     int(workspace_bytes), v(stream)), "crn_hops_device")
+
+    def extract_device(self, spectra_ptr, n_frames, params, channels_ptr, n_chan, taper_ptr, out_ptr, stream=0):
+        """Baseband sample streams of n_chan channels (device pointers; params from extract_params): spectra_ptr [n_frames][fft_len]
+        complex float32, what fft_forward_device writes with frame_stride = fft_len / 2; channels_ptr [n_chan] EXTRACT_CHANNEL_DTYPE;
+        taper_ptr [out_len] float32 (extract_taper); out_ptr [n_chan][frames_per_stream out_len / 2] complex float32, every sample
+        written, at extract_rate(fs, fft_len, out_len).  Only enqueues."""
+        v = lambda ptr: C.c_void_p(ptr or None)      # noqa: E731
+        check(lib().crn_extract_device(self._h, v(spectra_ptr), n_frames, C.byref(params), v(channels_ptr), int(n_chan), v(taper_ptr), v(out_ptr),
+                                       v(stream)), "crn_extract_device")
 
     def cyclo_device(self, frames_ptr, n_epochs, params, epochs_ptr, segments_ptr, cyclo_ptr, profile_ptr=0, stream=0):
         """The strongest cyclic feature of every stored segment of n_epochs epochs (device pointers; params from cyclo_params): frames_ptr
