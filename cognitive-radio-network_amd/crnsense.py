@@ -58,6 +58,7 @@ EXPORTS = [
     "crn_cyclo_device", "crn_cyclo_zmin",
     "crn_hops_bytes", "crn_hops_workspace_bytes", "crn_hops_device", "crn_hop_forecast",
     "crn_extract_device",
+    "crn_resample_state_bytes", "crn_resample_device",
     "crn_comm_unique_id", "crn_comm_create", "crn_comm_local", "crn_comm_allgather", "crn_comm_gathered",
     "crn_comm_finish", "crn_comm_destroy", "crn_comm_local_addr", "crn_comm_wait", "crn_comm_info",
     "crn_last_error", "crn_abi_version", "crn_build_info",
@@ -310,6 +311,25 @@ EXTRACT_CHANNEL_DTYPE = [("stream", "<i4"), ("centre", "<i4"), ("reserved", "<i4
 EXTRACT_OUT_LENS = (16, 32, 64, 128, 256)
 
 
+class ResampleParams(C.Structure):
+    """crn_resample_params (crn_resample_device), 32 bytes."""
+    _fields_ = [("in_len", C.c_int32), ("out_cap", C.c_int32), ("taps", C.c_int32), ("phases", C.c_int32), ("first", C.c_int32),
+                ("reserved", C.c_int32 * 3)]
+
+
+class ResampleRow(C.Structure):
+    """crn_resample_row: ratio and offset of one row of crn_resample_device, 16 bytes."""
+    _fields_ = [("step", C.c_uint64), ("dphi", C.c_int32), ("reserved", C.c_int32)]
+
+
+# numpy views of the row records crn_resample_device reads (resample_rows fills them) and of the states it carries, 320 bytes a row
+RESAMPLE_ROW_DTYPE = [("step", "<u8"), ("dphi", "<i4"), ("reserved", "<i4")]
+RESAMPLE_STATE_DTYPE = [("pos", "<u8"), ("phase", "<u4"), ("taps", "<i4"), ("n_in", "<i8"), ("n_out", "<i8"), ("n_dropped", "<i8"),
+                        ("last_n_out", "<i4"), ("reserved", "<i4", (5,)), ("hist", "<c8", (32,))]
+RESAMPLE_TAPS = (8, 16, 32)
+RESAMPLE_PHASES = (32, 64, 128, 256)
+
+
 CFAR_METHODS = {"ca": CFAR_CA, "go": CFAR_GO, "so": CFAR_SO, "os": CFAR_OS}
 
 
@@ -462,6 +482,9 @@ def lib():
         L.crn_hop_forecast.argtypes = [C.c_void_p, C.c_int32, C.c_uint64, C.c_double, C.POINTER(C.c_double)]
         L.crn_extract_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(ExtractParams), C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
                                          C.c_void_p]
+        L.crn_resample_state_bytes.argtypes, L.crn_resample_state_bytes.restype = [C.c_int64], C.c_int64
+        L.crn_resample_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(ResampleParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.c_void_p]
         L.crn_ingest_create.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]
         L.crn_ingest_push.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
         L.crn_ingest_flush.argtypes = [C.c_void_p]
@@ -859,6 +882,73 @@ def extract_channels(records, stream=0, fft_len=None):
 def extract_rate(fs, fft_len, out_len):
     """Sample rate of the streams crn_extract_device writes: fs out_len / fft_len."""
     return float(fs) * int(out_len) / int(fft_len)
+
+
+def resample_params(in_len, out_cap, taps=16, phases=128, first=False):
+    """crn_resample_params: in_len samples of every input row, out_cap of every output row (resample_out_cap), T = taps, P = phases;
+    first: the states' contents mean nothing."""
+    return ResampleParams(in_len=int(in_len), out_cap=int(out_cap), taps=int(taps), phases=int(phases), first=int(bool(first)))
+
+
+def resample_rows(ratio, offset=0.0):
+    """Row records (RESAMPLE_ROW_DTYPE) of crn_resample_device, one per entry of `ratio`: step = rint(ratio 2^32), ratio in input
+    samples per output sample (resample_ratio); dphi = rint(offset 2^32) wrapped to int32, `offset` in cycles per OUTPUT sample, the
+    frequency the mixer adds.  Either may be a scalar.  A ratio outside 1/4 .. 4 makes a row that the stage answers with zeros; ValueError
+    for a ratio or an offset that is not finite."""
+    import numpy as np
+    ratio, offset = np.broadcast_arrays(np.atleast_1d(np.asarray(ratio, np.float64)), np.asarray(offset, np.float64))
+    out = np.zeros(ratio.size, np.dtype(RESAMPLE_ROW_DTYPE))
+    if not (np.isfinite(ratio).all() and np.isfinite(offset).all()):
+        raise ValueError(f"resample_rows: ratio and offset must be finite, not {ratio.tolist()}, {offset.tolist()}")
+    for i, (rho, off) in enumerate(zip(ratio.reshape(-1), offset.reshape(-1))):
+        step = int(np.rint(rho * 2.0 ** 32)) if 0 <= rho < 2.0 ** 31 else 0
+        dphi = (int(np.rint(off * 2.0 ** 32)) + 2 ** 31) % 2 ** 32 - 2 ** 31
+        out[i] = (step, dphi, 0)
+    return out
+
+
+def resample_out_cap(in_len, min_ratio):
+    """The most outputs a call of in_len input samples can give a row whose ratio is at least min_ratio: step 1's n at pos = 0."""
+    import numpy as np
+    step = int(np.rint(float(min_ratio) * 2.0 ** 32))
+    if int(in_len) < 1 or not 2 ** 30 <= step <= 2 ** 34:
+        raise ValueError(f"resample_out_cap: in_len >= 1 and min_ratio in 1/4 .. 4, not {in_len}, {min_ratio}")
+    return ((int(in_len) << 32) - 1) // step + 1
+
+
+def resample_state_bytes(n_rows):
+    """Bytes of the states of n_rows rows (320 each)."""
+    nb = lib().crn_resample_state_bytes(int(n_rows))
+    if nb < 0:
+        raise ValueError(f"resample_state_bytes: n_rows must be in 0..65536, not {n_rows}")
+    return nb
+
+
+def resample_ratio(out_len, symbol_bins, sps):
+    """Input samples per output sample that bring a stream of crn_extract_device (out_len = M) to sps samples per symbol, for a symbol
+    rate of symbol_bins bins (cyclo_bins): out_len / symbol_bins / sps.  ValueError for a rate of 0 (nothing was found)."""
+    if not symbol_bins > 0 or not sps > 0:
+        raise ValueError(f"resample_ratio: symbol rate and samples per symbol must be positive, not {symbol_bins}, {sps}")
+    return float(out_len) / float(symbol_bins) / float(sps)
+
+
+def resample_delay(taps):
+    """Input samples by which the output of crn_resample_device lags its position, for a table of resample_taps: T / 2."""
+    return int(taps) // 2
+
+
+def resample_taps(taps, phases, cutoff, beta):
+    """The polyphase table h of crn_resample_device as float32 [phases + 1][taps]: h[phi][k] = g(k - T / 2 + phi / P), g(t) = 2 fc
+    sinc(2 fc t) I0(beta sqrt(1 - (2 t / T)^2)) / I0(beta) for |t| < T / 2 and 0 beyond, fc = cutoff in cycles per input sample; scaled
+    once so that the entries of rows 0 .. P - 1 sum to P.  Computed in float64 and rounded once."""
+    import numpy as np
+    T, P = int(taps), int(phases)
+    if T not in RESAMPLE_TAPS or P not in RESAMPLE_PHASES or not 0 < cutoff <= 0.5 or not beta >= 0:
+        raise ValueError(f"resample_taps: taps in {RESAMPLE_TAPS}, phases in {RESAMPLE_PHASES}, 0 < cutoff <= 0.5, beta >= 0, not {taps}, {phases}, {cutoff}, {beta}")
+    t = np.arange(T, dtype=np.float64)[None, :] - T // 2 + np.arange(P + 1, dtype=np.float64)[:, None] / P
+    inside = np.abs(t) < T / 2
+    g = np.where(inside, 2 * cutoff * np.sinc(2 * cutoff * t) * np.i0(beta * np.sqrt(np.where(inside, 1 - (2 * t / T) ** 2, 0.0))) / np.i0(beta), 0.0)
+    return (g * (P / g[:P].sum())).astype(np.float32)
 
 
 def hop_params(n_channels, epochs_per_stream, lags=(1,), first=False):
@@ -1310,6 +1400,16 @@ class Sensor:
         v = lambda ptr: C.c_void_p(ptr or None)      # noqa: E731
         check(lib().crn_extract_device(self._h, v(spectra_ptr), n_frames, C.byref(params), v(channels_ptr), int(n_chan), v(taper_ptr), v(out_ptr),
                                        v(stream)), "crn_extract_device")
+
+    def resample_device(self, in_ptr, n_rows, params, rows_ptr, taps_ptr, state_ptr, out_ptr, stream=0):
+        """n_rows sample streams resampled and mixed (device pointers; params from resample_params): in_ptr [n_rows][in_len] complex
+        float32, the rows extract_device writes as they are; rows_ptr [n_rows] RESAMPLE_ROW_DTYPE (resample_rows); taps_ptr
+        [phases + 1][taps] float32 (resample_taps); state_ptr resample_state_bytes(n_rows) of RESAMPLE_STATE_DTYPE, read unless
+        params.first and then rewritten; out_ptr [n_rows][out_cap] complex float32, every sample written, of which the state's
+        last_n_out are outputs.  Only enqueues."""
+        v = lambda ptr: C.c_void_p(ptr or None)      # noqa: E731
+        check(lib().crn_resample_device(self._h, v(in_ptr), int(n_rows), C.byref(params), v(rows_ptr), v(taps_ptr), v(state_ptr), v(out_ptr),
+                                        v(stream)), "crn_resample_device")
 
     def cyclo_device(self, frames_ptr, n_epochs, params, epochs_ptr, segments_ptr, cyclo_ptr, profile_ptr=0, stream=0):
         """The strongest cyclic feature of every stored segment of n_epochs epochs (device pointers; params from cyclo_params): frames_ptr

@@ -1131,6 +1131,93 @@ typedef struct crn_extract_channel {
 CRN_API int crn_extract_device(crn_handle *h, const float *d_spectra, int64_t n_frames, const crn_extract_params *params,
                                const crn_extract_channel *d_channels, int32_t n_chan, const float *d_taper, float *d_out, void *stream);
 
+/* -- resampling: an extracted stream at k samples per symbol -----------------------------------------------------------------------
+ * The extraction's streams run at fs M / N, whatever the emitter's symbol rate, and keep the offset between the emitter and the whole
+ * bin kappa.  This stage takes both away on the device: an arbitrary-ratio polyphase resampler with a fine mixer behind it.  The ratio
+ * and the offset are per row and read from device memory, so that a later stage can write them; the carry from call to call lies in
+ * the caller's device memory, as for the other stateful stages.
+ * T = taps, one of 8, 16, 32.  P = phases, one of 32, 64, 128, 256; s = 32 - log2 P.  d_in is [n_rows][in_len] interleaved complex fp32
+ * (the rows of crn_extract_device's d_out fit as they are); row r of the input is row r of d_rows, d_state and d_out.  d_taps is
+ * [P + 1][T] fp32, the polyphase table h, supplied by the caller as the extraction's taper is.  A row record holds step, the input
+ * samples per output sample in Q32.32 (rho = step / 2^32), and dphi, the mixer's increment per output sample in turns 2^32 (it wraps).
+ * A row is LIVE when 2^30 <= step <= 2^34 (rho from 1/4 to 4); any other value gives a row of zero bytes and last_n_out = 0, and the
+ * rest of its state stays as it was.  The state of a row is 320 bytes, a 64-byte head and hist[32] complex fp32; it is taken as EMPTY
+ * (pos 0, phase 0, a history of zeros, counters 0) when `first` is set or when its `taps` is not the call's T; a negative counter is
+ * read as 0.  No index is ever formed from a state's bytes except through pos, which enters the arithmetic of steps 1 and 6 only.
+ * For a live row, L = in_len 2^32, and x[i] for i < 0 is the history, x[i] = hist[T - 1 + i]:
+ *   1. count     n = 0 if pos >= L, else floor((L - 1 - pos) / step) + 1: the outputs whose position falls inside this call's input.
+ *                w = min(n, out_cap).
+ *   2. position  for u = 0 .. w - 1: p = pos + u step (no overflow: p < L <= 2^56); j = p >> 32; f = p mod 2^32; phi = f >> s;
+ *                mu = ((f mod 2^s) >> max(s - 24, 0)) 2^-min(s, 24), which fp32 holds exactly.
+ *   3. filter    y = sum over k = 0 .. T - 1 of ((1 - mu) h[phi][k] + mu h[phi + 1][k]) x[j - k].  Causal: with h from the rule below the
+ *                output sits T / 2 input samples behind position p.
+ *   4. mixer     z = y e^(+j 2 pi theta / 2^32), theta = phase + u dphi mod 2^32.
+ *   5. row       d_out[r][u] = z for u < w; every other sample of the row, up to out_cap, is zero bytes: every byte is written.
+ *   6. carry     pos <- pos + n step - L (pos - L when n = 0); phase <- phase + n dphi; n_in += in_len; n_out += w; n_dropped += n - w;
+ *                last_n_out = w; taps = T; hist <- the last T - 1 samples of (old history ++ this call's row), also for in_len < T - 1;
+ *                hist[T - 1 .. 31] and the reserved words are written as 0.  pos and phase advance by n, not w: outputs that did not fit
+ *                are lost, the stream's timing is not.
+ *   7. safety    whatever bytes the rows and the states hold, only d_in rows inside the batch, the table and the row's own state are
+ *                read, and only the row's own output and state written.
+ *   8. cutting   a row fed in one call, and the same row cut into calls of any lengths, give the same output samples bit for bit
+ *                (concatenated over last_n_out) and the same final state byte for byte (last_n_out apart, which speaks of the last call
+ *                alone); so does the same call repeated from the same state.  The arithmetic of one output therefore does not depend
+ *                on where the call begins: the history and the row are read through one path, and the sum over k runs in one order.
+ * Exactness: steps 1, 2, 5 and 6 are integers and exact.  For steps 3 and 4, with u = 2^-24, every output is within
+ * gamma u sum over k of max(|h[phi][k]|, |h[phi + 1][k]|) |x[j - k]| of the exact value, gamma = T + 12: 3 u for the interpolated
+ * coefficient (a rounded difference and one fma, mu exact), T u for the T-term sum, 5.7 u for the mixer factor (each component within
+ * 4 u of exact) and 2.4 u for the complex product.  theta is an integer, so its reduction to a quadrant is exact; what is left has 29
+ * bits and a sign, which fp32 holds to 0.8 u in the angle.
+ *   Table        crnsense.resample_taps(taps, phases, cutoff, beta), in float64, rounded once: h[phi][k] = g(k - T / 2 + phi / P) for
+ *                phi = 0 .. P, g(t) = 2 fc sinc(2 fc t) I0(beta sqrt(1 - (2 t / T)^2)) / I0(beta) for |t| < T / 2 and 0 beyond, fc =
+ *                cutoff in cycles per input sample, the whole scaled once so that rows 0 .. P - 1 sum to P (unit gain at 0).
+ *   Limits       the filter is short.  16 taps have a transition band of about +-0.16 cycles per sample around the cutoff (8 taps
+ *                +-0.18, 32 taps +-0.10): the signal must lie that far inside `cutoff`, and for rho > 1 `cutoff` must lie that far
+ *                inside 0.5 / rho.  With T 16, P 128, beta 8, cutoff 0.40 tones out to 0.22 come out within 1.1e-4 of their amplitude
+ *                sum, tones at 0.30 are 2 % off.  rho within 1/4 .. 4.  One table per call: rows of very different rho want separate
+ *                calls.  The delay is T / 2 input samples.  No timing recovery, no matched filter. */
+typedef struct crn_resample_params {
+  int32_t in_len;            /* 1 .. 2^24 samples of a row */
+  int32_t out_cap;           /* 1 .. 2^26 samples of an output row */
+  int32_t taps;              /* T: 8, 16 or 32 */
+  int32_t phases;            /* P: 32, 64, 128 or 256 */
+  int32_t first;             /* != 0: the states' contents mean nothing, start afresh */
+  int32_t reserved[3];       /* 0 */
+} crn_resample_params; /* 32 bytes */
+typedef struct crn_resample_row {
+  uint64_t step;             /* input samples per output sample, Q32.32; live in 2^30 .. 2^34 */
+  int32_t dphi;              /* mixer increment per output sample, turns 2^32 */
+  int32_t reserved;          /* not looked at */
+} crn_resample_row; /* 16 bytes */
+typedef struct crn_resample_state {
+  uint64_t pos;              /* Q32.32 position of the next output, relative to the first sample of the next call's input */
+  uint32_t phase;            /* mixer phase, turns 2^32 */
+  int32_t taps;              /* the T this history belongs to */
+  int64_t n_in;              /* input samples taken so far */
+  int64_t n_out;             /* output samples produced so far */
+  int64_t n_dropped;         /* outputs that did not fit */
+  int32_t last_n_out;        /* outputs written by the last call */
+  int32_t reserved[5];       /* written as 0 */
+  float hist[64];            /* hist[32] complex: the last T - 1 input samples in [0 .. T - 2], the rest written as 0 */
+} crn_resample_state; /* 320 bytes */
+
+/* Bytes of n_rows states: 320 n_rows, -1 for n_rows outside 0 .. 65536.  Needs no handle and no device. */
+CRN_API int64_t crn_resample_state_bytes(int64_t n_rows);
+
+/* Enqueue the stage on `stream`, two launches (device pointers, all 16-byte aligned):
+ *   d_in     [n_rows][in_len] complex fp32
+ *   d_rows   [n_rows]                        the row records
+ *   d_taps   [phases + 1][taps] fp32         h
+ *   d_state  [n_rows]                        the states: read (unless first != 0), then rewritten by the second launch
+ *   d_out    [n_rows][out_cap] complex fp32, every sample written
+ * `h` supplies the device only.  Only enqueues; allocates nothing, needs no workspace.  No atomics: the same call from the same state
+ * gives the same bytes.  CRN_ERR_ARG, decided before any device call, for a NULL h, params, d_in, d_rows, d_taps, d_state or d_out;
+ * taps or phases not in the list; in_len outside 1 .. 2^24; out_cap outside 1 .. 2^26; n_rows outside 0 .. 65536; a nonzero reserved
+ * in params; any of the five arrays not 16-byte aligned.  n_rows = 0 succeeds and launches nothing. */
+CRN_API int crn_resample_device(crn_handle *h, const float *d_in, int32_t n_rows, const crn_resample_params *params,
+                                const crn_resample_row *d_rows, const float *d_taps, crn_resample_state *d_state, float *d_out,
+                                void *stream);
+
 /* Allocate, now, the device scratch and pinned staging that crn_sense_run_host needs for up to
  * max_epochs dense epochs of full-length frames (and their per-bin spectra when want_spectrum != 0),
  * and load the kernels: a later crn_sense_run_host within that size allocates nothing.  An engine
